@@ -6,6 +6,14 @@ Poisson matrix (default 128^3, BASELINE config C3/C5), values already resident i
 Prints ONE JSON line (rank 0).  Launch: ``python bench.py`` (1 GPU) or, for N GPUs,
 ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N``.
 
+A plain run sets up, warms up, times `--steps` refactorizations and prints the line (metric, value,
+ms_per_step, the per-kernel HIP-event times of those same steps).  `--full` adds, after the timed
+steps, everything else: solves and their residual, the refactor with host values, the ordering
+comparison, the CPU baselines and the C1/C2/C5 configs (`--no-cpu`, `--no-configs`: the full run
+without those legs).  `--dump-outputs DIR` writes what the last
+timed step computed as DIR/<name>.npy; the inputs are seeded, so two builds run with the same
+arguments can be compared file by file.
+
 Multi-GPU (N > 1): ONE factorization split over the ranks — subtrees of the assembly tree per
 rank, update blocks moved at exchange points over RCCL point-to-point ("scaling": "strong";
 `--replicas` runs independent copies instead).  DESIGN.md §7.
@@ -238,6 +246,69 @@ def kernel_source_sha():
     return hs.hexdigest()[:12]
 
 
+DUMP_FACTOR_DOUBLES = 1 << 21   # --dump-outputs: sampled doubles of the factor store (16 MiB)
+DUMP_CHUNK = 4096               # ... read in runs of this many consecutive doubles
+DUMP_SEED = 47
+
+
+def factor_sample(F, total=DUMP_FACTOR_DOUBLES, chunk=DUMP_CHUNK, seed=DUMP_SEED):
+    """A fixed sample of the factor values a one-GPU handle holds (128^3: 2.9e9 doubles, far more
+    than a dump may hold).  The values are the fronts' L panels (M x ns) and U12 blocks (ns x nu)
+    laid end to end in front order; `total // chunk` run starts are drawn from default_rng(seed)
+    over that concatenation (so a front is sampled in proportion to its size) and each run is
+    `chunk` doubles, cut at the end of its block.  The plan fixes the layout, so two builds with
+    the same plan sample the same entries.  Returns (values, store offsets of the runs)."""
+    from smlu import _lib as C
+    L = C.lib()
+    ns = int(F.stat("nsuper"))
+    off = np.empty(4 * ns, np.int64)
+    rc = L.smlu_dev_front_offsets(F._h, C.ptr(off))
+    assert rc == 0, C.last_error(F._h)
+    off = off.reshape(ns, 4)
+    w = np.diff(F.fronts()["first"])                 # pivot columns per front
+    M = off[:, 3]
+    start = np.concatenate([off[:, 0], off[:, 1]])   # L panels, then U12 blocks
+    length = np.concatenate([M * w, w * (M - w)])
+    keep = length > 0
+    start, length = start[keep], length[keep]
+    cum = np.concatenate([[0], np.cumsum(length)])
+    assert cum[-1] > 0, "the handle holds no factor values"
+    nrun = max(1, min(total // chunk, int(cum[-1]) // chunk))
+    at = np.sort(np.random.default_rng(seed).integers(0, cum[-1], size=nrun))
+    seg = np.searchsorted(cum, at, side="right") - 1
+    vals, offs = [], []
+    for a, s in zip(at, seg):
+        o = int(start[s] + (a - cum[s]))
+        cnt = int(min(chunk, start[s] + length[s] - o))
+        buf = np.empty(cnt)
+        rc = L.smlu_dev_copy(F._h, 0, o, cnt, C.ptr(buf), None)   # range-checked by the library
+        assert rc == 0, C.last_error(F._h)
+        vals.append(buf)
+        offs.append(o)
+    return np.concatenate(vals), np.asarray(offs, np.float64)
+
+
+def dump_outputs(path, F, x, partitioned, rank):
+    """--dump-outputs: what the last timed refactor left in the handle, as float64 .npy files (32.6 MB
+    at 128^3; 33.6 MB if no run were cut): `x`, the solution of A x = b on those factors (b = default_rng(5): the whole
+    factorization, pivots and row scaling included, in one vector), and on one GPU a seeded sample
+    of the factor values (factor_sample) with the store offsets of its runs.  F.p, F.q and F.Rs are
+    left out: the library hands them out only with a host export of all of L and U (47 GB here);
+    F.perm_scale() does not avoid that, it passes NULL factor pointers to smlu_get_factors, which
+    builds the whole export before it looks at them."""
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    if x.size > DUMP_FACTOR_DOUBLES:   # sides above 128: entries at sorted indices from the seed
+        x = x[np.sort(np.random.default_rng(DUMP_SEED).choice(x.size, DUMP_FACTOR_DOUBLES, replace=False))]
+    out = {"x": x}
+    if not partitioned:
+        out["factor_sample"], out["factor_sample_offsets"] = factor_sample(F)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    log(f"wrote {sorted(out)} to {path} ({sum(a.size for a in out.values()) * 8 / 1e6:.1f} MB)")
+
+
 def max_over_ranks(x, device=None):
     """Max of a float over all ranks (identity when torch.distributed is not initialised)."""
     import torch
@@ -321,7 +392,17 @@ def launch_check(rank, world, local):
     return 0
 
 
-def main():
+def side_legs(args, world, partitioned):
+    """Which side measurements run after the timed steps: (full, cpu, configs).  `full` (solves and
+    their residual, the refactor with host values) is asked for by --full, by --no-cpu / --no-configs
+    (they name a leg of the full run to leave out) and by --check-single on a partitioned run (it
+    compares solutions); `cpu` (ordering comparison, CPU baselines) and `configs` (C1/C2/C5) are
+    legs of the full run on one GPU."""
+    full = bool(args.full or args.no_cpu or args.no_configs or (args.check_single and partitioned))
+    return full, full and not args.no_cpu and world == 1, full and not args.no_configs and world == 1
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -329,8 +410,16 @@ def main():
     ap.add_argument("--side", "--n", dest="n", type=int, default=128,
                     help="grid side of the 3D Poisson workload")
     ap.add_argument("--ordering", default="nd", choices=["nd", "geometric"])
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C1/C2/C5 side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: solves and "
+                         "their residual, the refactor with host values, the ordering comparison, the CPU "
+                         "baselines and the C1/C2/C5 configs (minutes; a plain run skips all of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy "
+                         "(float64, under 64 MB; see dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU legs (implies --full)")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="--full without the C1/C2/C5 side measurements (implies --full)")
     ap.add_argument("--no-profile", action="store_true", help="skip per-kernel HIP events")
     ap.add_argument("--test-one-gpu", action="store_true",
                     help="rehearsal: all ranks on cuda:0, gloo transport (never for measurements)")
@@ -339,13 +428,18 @@ def main():
                          "(device buffers on the library's stream) carried over gloo")
     ap.add_argument("--check-single", action="store_true",
                     help="partitioned run: after the timed steps, rank 0 factors the last values on one GPU "
-                         "and every rank's solution is compared with that one (rehearsals, VERDICT r05)")
+                         "and every rank's solution is compared with that one (rehearsals, VERDICT r05); "
+                         "the line then also carries --full's solve time and residual")
     ap.add_argument("--replicas", action="store_true",
                     help="N > 1: independent replicas instead of the partitioned factorization")
     ap.add_argument("--launch-check", action="store_true",
                     help="launcher check only: every rank reports (rank, world) over gloo, rank 0 prints "
                          "one JSON line; no GPU call (tests/test_bench_launch.py)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     # --gpus N without a launcher: start the N ranks here, before anything touches the GPU, as
     # child processes of torch.distributed.run (never an exec), and exit with their status.
@@ -417,18 +511,25 @@ def main():
             f"{F.stat('refactor_ms_last'):.1f} ms")
 
     dt = timed_region(step, args.steps, args.warmup, torch.cuda.synchronize)
-    # one solve (reported, not the metric)
-    b = torch.from_numpy(np.random.default_rng(5).random(n)).to(dev)   # same b on every rank
-    x = torch.empty_like(b)
-    F.solve_device(x, b)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    F.solve_device(x, b)
-    torch.cuda.synchronize()
-    solve_ms = (time.perf_counter() - t1) * 1e3
+    full, cpu_leg, configs_leg = side_legs(args, world, partitioned)
+    solve_ms = solve8_ms = solve_residual = refactor_host_ms = None
+    xh = None
+    if full or args.dump_outputs:
+        # one solve on the last timed step's factors (reported under --full, not the metric)
+        b = torch.from_numpy(np.random.default_rng(5).random(n)).to(dev)   # same b on every rank
+        x = torch.empty_like(b)
+        F.solve_device(x, b)
+        torch.cuda.synchronize()
+        xh = x.cpu().numpy()
+    if args.dump_outputs:   # before anything below refactors again
+        dump_outputs(args.dump_outputs, F, xh, partitioned, rank)
+    if full:
+        t1 = time.perf_counter()
+        F.solve_device(x, b)
+        torch.cuda.synchronize()
+        solve_ms = (time.perf_counter() - t1) * 1e3
     # eight right-hand sides in one batched call (single GPU)
-    solve8_ms = None
-    if not partitioned and hasattr(F, "solve_multi_device"):
+    if full and not partitioned and hasattr(F, "solve_multi_device"):
         B8 = torch.from_numpy(np.random.default_rng(6).random((8, n))).to(dev)
         X8 = torch.empty_like(B8)
         F.solve_multi_device(X8, B8)
@@ -437,16 +538,16 @@ def main():
         F.solve_multi_device(X8, B8)
         torch.cuda.synchronize()
         solve8_ms = (time.perf_counter() - t1) * 1e3
-    # residual of that solve on the last refactored values (host SpMV)
-    Al = A.copy()
-    Al.data = vals[-1].cpu().numpy()
-    xh, bh = x.cpu().numpy(), b.cpu().numpy()
-    solve_residual = float(np.abs(Al @ xh - bh).max() / np.abs(bh).max())
+    if full:
+        # residual of that solve on the last refactored values (host SpMV)
+        Al = A.copy()
+        Al.data = vals[-1].cpu().numpy()
+        bh = b.cpu().numpy()
+        solve_residual = float(np.abs(Al @ xh - bh).max() / np.abs(bh).max())
     # lu!(F, A) with HOST values (the Julia shim's smlu_refactor: pageable upload of the values, the
     # dominance test on the device, the factorization) -- a side figure beside the resident-values
     # metric (within 3 % of ms_per_step)
-    refactor_host_ms = None
-    if not partitioned:
+    if full and not partitioned:
         hv = [vals[r % len(vals)].cpu().numpy() for r in range(2)]
         F.refactor(hv[1])
         th = []
@@ -565,25 +666,25 @@ def main():
             # kernel, profiles/) over this run's time per refactor
             "achieved_hbm_GBs": (hbm_refactor / (ms_per_step * 1e-3) / 1e9) if hbm_refactor else None,
             "achieved_hbm_frac": (hbm_refactor / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS) if hbm_refactor else None,
-            "refactor_host_values_ms": refactor_host_ms,
-            "solve_ms": solve_ms,
-            "solve_8rhs_ms": solve8_ms,
-            "solve_residual": solve_residual,
             "create_s": t_create,
             "ranks": per_rank,
+            "full": full,
         }
+        if full:   # the side measurements a plain run skips
+            res.update({"refactor_host_values_ms": refactor_host_ms, "solve_ms": solve_ms,
+                        "solve_8rhs_ms": solve8_ms, "solve_residual": solve_residual})
         if partitioned:
             res["rccl_nranks"] = min(r.get("rccl_nranks", 0) for r in per_rank)
             res["transport"] = (f"{args.one_gpu_transport} (gloo, one-GPU rehearsal)" if args.test_one_gpu
                                 else "rccl")
             if args.check_single:
                 res["x_vs_single_gpu_max_rel"] = max(r["x_vs_single_gpu_max_rel"] for r in per_rank)
-        if not args.no_cpu and world == 1:
+        if cpu_leg:
             log("ordering comparison (host symbolic analysis) ...")
             res["config"]["ordering_compare"] = ordering_compare(N)
             log("cpu baseline ...")
             res["cpu_baseline"] = cpu_baseline(N, dense_flops, nnzLU, args.ordering == "geometric")
-        if not args.no_configs and world == 1:
+        if configs_leg:
             log("configs C1 / C2 / C5 steady state ...")
             res["configs"] = gpu_configs(dev)
         print(json.dumps(res), flush=True)
