@@ -350,6 +350,16 @@ int smlu_dev_front_hash(smlu_handle* h, unsigned long long* out);
 int smlu_dev_front_values(smlu_handle* h, int64_t s, double* out);
 int smlu_dev_front_offsets(smlu_handle* h, int64_t* out);
 int smlu_dev_copy(smlu_handle* h, int which, int64_t off, int64_t cnt, double* out, int64_t* len);
+/* Host-only: section hashes of rank `rank`'s schedule of a `nparts`-rank handle (launches, tasks,
+ * work lists, communication steps), so that a CPU test sees any change of what is scheduled.
+ * flags: bit 0 values not diagonally dominant, bit 1 pivmode = 1 (the re-pivoting refactor's
+ * schedule), bit 2 pair-preserving pivots (complex handle), bit 3 use_mfma = 0.  Writes *len words
+ * (out = NULL: only *len): 19 section hashes (node records | fac, fwd, bwd, fwdm, bwdm | segments |
+ * comm | ilist, xt, ae, xc, ft, gptr, gent | gt, st_tasks, ur_tasks | scalars), the launch counts
+ * per kind of fac, fwd and bwd, the numbers of exchange and broadcast steps, and the bit patterns
+ * of gemm_flops, gemm22_flops, gemm_bytes and smlu_plan_rank_schedule's bytes[0..4]. */
+int smlu_plan_schedule_digest(const smlu_plan* plan, int32_t nparts, int32_t rank, int32_t flags, uint64_t* out,
+                              int64_t cap, int64_t* len);
 
 /* ---- environment knobs (read by the library in one place, csrc/tune.cpp; nothing else in the
  * environment changes its numerics or schedule) ---------------------------------------------

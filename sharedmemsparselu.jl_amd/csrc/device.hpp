@@ -70,6 +70,12 @@ struct XContrib {
   int64_t src;
 };
 
+// One A entry of an assembly or small-front work list: x = entry id, y = local row (k_assemble) or
+// local column << 16 | local row (k_front_small).  Same layout as HIP's int2, which the kernels read.
+struct alignas(8) AEnt {
+  int32_t x, y;
+};
+
 // Device-to-device copy of n4 4-byte words (the pack / unpack steps of the multi-GPU exchanges).
 struct SegDesc {
   uint64_t src, dst;

@@ -78,7 +78,7 @@ int rccl_allreduce_max(void* ctx, double* buf, int32_t count) {
 }  // namespace smlu
 
 int exec_comm(smlu_handle* h, int id) {
-  CommOp& op = h->comm[id];
+  CommOp& op = h->sch.comm[id];
   hipStream_t st = h->stream;
   HIPCHK(launch_segcopy(st, h->segdesc.p + op.pack0, (int64_t)op.pack.size()));
   char* base[10] = {(char*)h->store.p, (char*)h->scratch.p, (char*)h->vbuf.p, (char*)h->wrk.p,
@@ -239,38 +239,59 @@ double smlu_plan_project(const smlu_plan* plan, int32_t nparts, double tflops, d
 }
 
 
+// A rank's schedule built on the host, as setup_device builds it but with no device: the plan
+// copied and partitioned, the rank's layout, the schedule and the bytes it would allocate.
+// flags: smlu_plan_schedule_digest's (0: dominant values, pivmode 0, real, MFMA).
+namespace {
+struct HostSchedule {
+  Plan plan;
+  RankLayout lay;
+  Schedule sch;
+  double bytes[5] = {0};
+};
+int host_schedule(const smlu_plan* plan, int32_t nparts, int32_t rank, int32_t flags, HostSchedule& H) {
+  try {
+    H.plan = plan->plan;   // copy: the partition is this query's
+    ScheduleInput in;
+    in.plan = &H.plan;
+    in.lay = &H.lay;
+    in.tn = tune();
+    in.rank = rank;
+    in.nranks = nparts;
+    in.dominant = !(flags & 1);
+    in.pivmode = (flags & 2) ? 1 : 0;
+    in.cpair = (flags & 4) != 0;
+    in.use_mfma = !(flags & 8);
+    if (in.tn.ob > 0) in.ob = in.tn.ob;
+    if (nparts > 1) H.plan.compute_owners(nparts, in.ob);
+    rank_layout_of(H.plan, rank, nparts, H.lay);
+    const std::string e = build_schedule(in, H.sch);
+    if (!e.empty()) return fail(nullptr, H.sch.err_code, e);
+    schedule_bytes(H.plan, H.lay, H.sch, rank, nparts, H.bytes);
+  } catch (const std::bad_alloc&) {
+    return fail(nullptr, SMLU_ERR_ALLOC, "host allocation failed");
+  }
+  return SMLU_OK;
+}
+}  // namespace
+
 int smlu_plan_rank_schedule(const smlu_plan* plan, int32_t nparts, int32_t rank, int64_t* ops, int64_t cap,
                             int64_t* len, double bytes[5], int64_t counts[3]) {
   if (!plan || !len || nparts < 1 || rank < 0 || rank >= nparts || (ops && cap < 0))
     return fail(nullptr, SMLU_ERR_ARG, "invalid arguments");
-  std::unique_ptr<smlu_handle> h(new (std::nothrow) smlu_handle());
-  if (!h) return fail(nullptr, SMLU_ERR_ALLOC, "allocation failed");
-  smlu_default_opts(&h->opts);
-  h->opts.index_base = 0;
-  int rc = SMLU_OK;
-  try {
-    h->plan = plan->plan;   // copy: the partition is this query's
-    h->rank = rank;
-    h->nranks = nparts;
-    h->dominant = true;     // the collective schedule does not depend on the pivoting mode
-    if (nparts > 1) {
-      if (tune().ob > 0) h->ob = tune().ob;
-      h->plan.compute_owners(nparts, h->ob);
-    }
-    rc = build_schedule_host(h.get());
-  } catch (const std::bad_alloc&) {
-    return fail(nullptr, SMLU_ERR_ALLOC, "host allocation failed");
-  }
-  if (rc != SMLU_OK) return fail(nullptr, rc, h->err);
+  HostSchedule H;   // dominant values: the collective schedule does not depend on the pivoting mode
+  const int rc = host_schedule(plan, nparts, rank, 0, H);
+  if (rc != SMLU_OK) return rc;
+  const Schedule& S = H.sch;
   int64_t k = 0;
   auto put = [&](int64_t v) {
     if (ops && k < cap) ops[k] = v;
     ++k;
   };
-  const std::vector<int>* seqs[3] = {&h->fac_comm, &h->fwd_comm, &h->bwd_comm};
+  const std::vector<int>* seqs[3] = {&S.fac_comm, &S.fwd_comm, &S.bwd_comm};
   for (int q = 0; q < 3; ++q)
     for (int id : *seqs[q]) {
-      const CommOp& op = h->comm[id];
+      const CommOp& op = S.comm[id];
       put(q);
       put(op.type);
       put(op.type == 1 ? op.root : -1);
@@ -289,15 +310,31 @@ int smlu_plan_rank_schedule(const smlu_plan* plan, int32_t nparts, int32_t rank,
     }
   *len = k;
   if (bytes)
-    for (int i = 0; i < 5; ++i) bytes[i] = h->host_bytes[i];
+    for (int i = 0; i < 5; ++i) bytes[i] = H.bytes[i];
   if (counts) {
-    counts[0] = (int64_t)h->fac.size();
+    counts[0] = (int64_t)S.fac.size();
     int64_t sh = 0;
-    for (int64_t s = 0; s < h->plan.nsup && nparts > 1; ++s)
-      if (h->plan.dist(s) && std::binary_search(h->plan.group[s].begin(), h->plan.group[s].end(), rank)) ++sh;
+    for (int64_t s = 0; s < H.plan.nsup && nparts > 1; ++s)
+      if (H.plan.dist(s) && std::binary_search(H.plan.group[s].begin(), H.plan.group[s].end(), rank)) ++sh;
     counts[1] = sh;
-    counts[2] = (int64_t)h->lay.blocks.size();
+    counts[2] = (int64_t)H.lay.blocks.size();
   }
   if (ops && k > cap) return fail(nullptr, SMLU_ERR_ARG, "ops buffer too small");
+  return SMLU_OK;
+}
+
+int smlu_plan_schedule_digest(const smlu_plan* plan, int32_t nparts, int32_t rank, int32_t flags, uint64_t* out,
+                              int64_t cap, int64_t* len) {
+  if (!plan || !len || nparts < 1 || rank < 0 || rank >= nparts || (out && cap < 0))
+    return fail(nullptr, SMLU_ERR_ARG, "invalid arguments");
+  HostSchedule H;
+  const int rc = host_schedule(plan, nparts, rank, flags, H);
+  if (rc != SMLU_OK) return rc;
+  std::vector<uint64_t> dg;
+  schedule_digest(H.sch, H.bytes, dg);
+  *len = (int64_t)dg.size();
+  if (!out) return SMLU_OK;
+  if ((int64_t)dg.size() > cap) return fail(nullptr, SMLU_ERR_ARG, "digest buffer too small");
+  std::copy(dg.begin(), dg.end(), out);
   return SMLU_OK;
 }

@@ -13,7 +13,7 @@ static hipError_t run_launch(smlu_handle* h, const Launch& L, double diag_tol, d
                                 h->rowperm.p, h->info.p, h->growth.p, diag_tol, piv_tol);
     case K_STEPTRSM:
       return launch_step_trsm(st, (int)L.aux, h->ftiles.p + L.off, (int)L.cnt, L.nwg, h->ftiles.p + L.off2,
-                              (int)L.cnt2, L.nwg2, L.step, h->ob, h->sn.p, h->store.p, h->scratch.p, h->info.p,
+                              (int)L.cnt2, L.nwg2, L.step, h->sch.ob, h->sn.p, h->store.p, h->scratch.p, h->info.p,
                               h->growth.p, piv_tol);
     case K_LASWP:
       return launch_laswp(st, L.nwg, h->stasks.p + L.off, (int)L.cnt, h->sn.p, h->store.p, h->scratch.p,
@@ -22,9 +22,9 @@ static hipError_t run_launch(smlu_handle* h, const Launch& L, double diag_tol, d
       return launch_panel1(st, (int)L.cnt, (int)L.aux, (int)L.nwg, (int)L.aux2, L.step,
                            h->ilist.p + L.off, h->sn.p,
                           h->store.p, h->scratch.p, h->rowperm.p, h->swaps.p, kSwapStride, h->info.p,
-                          h->growth.p, diag_tol, (int)L.cnt2, h->tinv.p, (int)h->ob);
+                          h->growth.p, diag_tol, (int)L.cnt2, h->tinv.p, (int)h->sch.ob);
     case K_TRSMU:
-      return launch_trsm_u(st, L.nwg, h->ftiles.p + L.off, (int)L.cnt, h->ob, (int)L.aux, h->sn.p,
+      return launch_trsm_u(st, L.nwg, h->ftiles.p + L.off, (int)L.cnt, h->sch.ob, (int)L.aux, h->sn.p,
                            h->store.p, h->scratch.p, h->swaps.p, kSwapStride);
     case K_GEMM:
     case K_GEMMU:
@@ -49,14 +49,14 @@ static hipError_t run_launch(smlu_handle* h, const Launch& L, double diag_tol, d
 static int enqueue_factor(smlu_handle* h, Timer& tm, bool dbg, int seg) {
   Plan& P = h->plan;
   hipStream_t st = h->stream;
-  const size_t lo = h->fac_seg[seg];
-  const size_t hi = (size_t)seg + 1 < h->fac_seg.size() ? h->fac_seg[seg + 1] : h->fac.size();
+  const size_t lo = h->sch.fac_seg[seg];
+  const size_t hi = (size_t)seg + 1 < h->sch.fac_seg.size() ? h->sch.fac_seg[seg + 1] : h->sch.fac.size();
   double diag_tol = P.given_order ? 0.0 : h->opts.diag_pivot_tol;
   double piv_tol = h->opts.pivot_tol;
   if (seg > 0) goto launches;
   // info words and growth cleared, identity (local) row permutation (fronts overwrite their part):
   // one kernel, so that the captured graph holds kernel nodes only
-  HIPCHK(launch_factor_reset(st, h->nnodes, h->info.p, h->growth.p, P.n, h->rowperm.p, h->rowperm0.p));
+  HIPCHK(launch_factor_reset(st, h->sch.nnodes, h->info.p, h->growth.p, P.n, h->rowperm.p, h->rowperm0.p));
   if (!h->given_Rs) {
     if (h->opts.scale) HIPCHK(launch_rowscale(st, P.n, h->Arowptr.p, h->Arow_ent.p, h->A.p, h->Rs.p));
     else HIPCHK(launch_fill(st, P.n, h->Rs.p, 1.0));
@@ -68,11 +68,11 @@ launches:
   // a join event after its last launch
   // (profile mode: a group is timed once, on the main stream from before the fork to after the
   // join, so the overlapped branches are not counted twice)
-  auto group = [&](size_t i) { return h->fac[i].kind == K_FRONT_LDS ? h->fac[i].aux2 : 0; };
+  auto group = [&](size_t i) { return h->sch.fac[i].kind == K_FRONT_LDS ? h->sch.fac[i].aux2 : 0; };
   int gi = 0;   // index of the current launch inside its group
   hipEvent_t gstop = nullptr;
   for (size_t li = lo; li < hi; ++li) {
-    const Launch& L = h->fac[li];
+    const Launch& L = h->sch.fac[li];
     const int64_t g = group(li);
     const bool cont = g > 0 && li > lo && group(li - 1) == g;
     const bool more = g > 0 && li + 1 < hi && group(li + 1) == g;
@@ -120,7 +120,7 @@ static int factor_segment(smlu_handle* h, Timer& tm, int seg) {
   const Tune tn = tune();
   const bool dbg = tn.debug_sync, nograph = tn.no_graph;
   const int prof = h->opts.profile ? 1 : 0;
-  const size_t nseg = h->fac_seg.size();
+  const size_t nseg = h->sch.fac_seg.size();
   if (h->fac_execs.size() != nseg || (seg == 0 && h->fac_exec_profile != prof)) {
     for (auto& g : h->fac_execs)
       if (g) (void)hipGraphExecDestroy(g);
@@ -183,7 +183,7 @@ static int finish_factor(smlu_handle* h, Timer& tm, std::chrono::steady_clock::t
   // words: the growth maximum (growth[0]) and the dominance flags of the values (growth[1], two
   // int32: by columns, by rows; written by k_dominance ahead of the factorization when the
   // pivoting mode is re-decided) -- one record, one synchronisation per factorization
-  int rs = read_status(h, h->info.p, h->nnodes, reinterpret_cast<const int32_t*>(h->growth.p), 4, rec);
+  int rs = read_status(h, h->info.p, h->sch.nnodes, reinterpret_cast<const int32_t*>(h->growth.p), 4, rec);
   if (rs != SMLU_OK) return rs;
   h->dom_words = rec[7];
   if (rec[10] > 0) {   // an info word no factor kernel writes: never read as a pivot status
@@ -209,7 +209,7 @@ static int finish_factor(smlu_handle* h, Timer& tm, std::chrono::steady_clock::t
   if (rec[2] >= 0) {
     const int32_t v = (int32_t)rec[3];
     rc = SMLU_SINGULAR;
-    h->errcol = P.s_first[h->node_front[rec[2]]] + ((v >> 2) > 0 ? (v >> 2) - 1 : 0);
+    h->errcol = P.s_first[h->sch.node_front[rec[2]]] + ((v >> 2) > 0 ? (v >> 2) - 1 : 0);
   }
   if (h->nranks > 1) {   // the pivot status of the whole partition, on every rank
     double red[3] = {rc == SMLU_SINGULAR ? 1.0 : 0.0, (double)h->errcol, (double)h->weak};
@@ -231,9 +231,9 @@ static int run_factor_once(smlu_handle* h) {
   for (auto& v : h->kind_ms) v = 0;
   h->comm_sent_fac = h->comm_recv_fac = 0;
   Timer tm(h);
-  for (size_t seg = 0; seg < h->fac_seg.size(); ++seg) {
+  for (size_t seg = 0; seg < h->sch.fac_seg.size(); ++seg) {
     if (seg > 0) {
-      int rc = exec_comm(h, h->fac_comm[seg - 1]);
+      int rc = exec_comm(h, h->sch.fac_comm[seg - 1]);
       if (rc != SMLU_OK) return rc;
     }
     int rc = factor_segment(h, tm, (int)seg);
@@ -273,7 +273,7 @@ int run_factor(smlu_handle* h, bool redecide) {
       h->opts.pivot_tol > 0 && !h->plan.given_order && h->nranks == 1) {
     h->repivot_node = h->flag_node;
     h->repivot_info = h->flag_info;
-    h->repivot_sn = h->flag_node >= 0 && h->flag_node < (int64_t)h->hsn.size() ? h->hsn[h->flag_node] : SNode{};
+    h->repivot_sn = h->flag_node >= 0 && h->flag_node < (int64_t)h->sch.hsn.size() ? h->sch.hsn[h->flag_node] : SNode{};
     h->repivot_growth = h->growth_max;
     h->pivmode = 1;
     int r2 = rebuild_schedule(h);
@@ -370,7 +370,7 @@ int smlu_dev_front_hash(smlu_handle* h, unsigned long long* out) {
 int smlu_dev_front_values(smlu_handle* h, int64_t s, double* out) {
   if (!h || !out || s < 0 || s >= h->plan.nsup) return fail(h, SMLU_ERR_ARG, "invalid arguments");
   if (h->nranks > 1) return fail(h, SMLU_ERR_STATE, "one-GPU handles only");
-  const SNode& r = h->hsn[s];
+  const SNode& r = h->sch.hsn[s];
   const int64_t M = (int64_t)r.ns + r.nu;
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(out, h->store.p + r.Loff, sizeof(double) * M * r.ns, hipMemcpyDeviceToHost));
@@ -398,7 +398,7 @@ int smlu_dev_copy(smlu_handle* h, int which, int64_t off, int64_t cnt, double* o
 int smlu_dev_front_offsets(smlu_handle* h, int64_t* out) {
   if (!h || !out) return fail(h, SMLU_ERR_ARG, "NULL argument");
   for (int64_t s = 0; s < h->plan.nsup; ++s) {
-    const SNode& r = h->hsn[s];
+    const SNode& r = h->sch.hsn[s];
     out[4 * s] = r.Loff;
     out[4 * s + 1] = r.Uoff;
     out[4 * s + 2] = r.Foff;

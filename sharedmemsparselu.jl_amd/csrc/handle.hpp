@@ -1,6 +1,7 @@
-// handle.hpp — internal to libsmlu.so: the handle, the launch records of its static schedule,
-// device buffers, the built-in RCCL transport and the host entry points shared by the units
-//   schedule.cpp  (schedule construction, device set-up)   factor.cpp  (refactorization)
+// handle.hpp — internal to libsmlu.so: the handle, its static schedule (schedule.hpp), device
+// buffers, the built-in RCCL transport and the host entry points shared by the units
+//   schedule_build.cpp (schedule construction, host only: schedule.hpp)   schedule_digest.cpp (its hashes)
+//   schedule.cpp  (device set-up, schedule upload)         factor.cpp  (refactorization)
 //   solve.cpp     (solves, refinement, chunked layout)     export.cpp  (factor export, pattern hand-over)
 //   complex.cpp   (ComplexF64 handles)                     dist.cpp    (RCCL, partitioned handles)
 //   smlu.cpp      (create / destroy / stats / plan API)
@@ -25,6 +26,7 @@
 #include "../../include/smlu.h"
 #include "device.hpp"
 #include "plan.hpp"
+#include "schedule.hpp"
 
 namespace smlu {
 hipError_t launch_rowscale(hipStream_t, int64_t, const int64_t*, const int32_t*, const double*, double*);
@@ -89,45 +91,7 @@ using namespace smlu;
 
 namespace smlu {
 
-constexpr int kSmallM = 128;     // fronts up to this order are factored whole in LDS
-constexpr int kFullPivNs = 512;  // blocked fronts up to this many pivots search all fully-summed rows
-constexpr int kNbFull = 32;
-constexpr int kNbTile = 64;
-constexpr int kSwapStride = 1 + 2 * 64;
-constexpr int kOBDefault = 384;   // outer block of the two-level blocked front factorization (256/384/512 within 1 %; 384 best)
-
 extern thread_local std::string g_last_error;
-
-enum Kind : int {
-  K_EXTADD, K_FRONT_LDS, K_PANEL, K_TRSMU, K_TRSML,
-  K_GEMM, K_FWD, K_BWD, K_FWDG, K_TRIF, K_BWDU, K_TRIB, K_GEMM22, K_LASWP, K_STEPTRSM, K_GEMMU,
-  K_GEMMO, K_TRIINV, K_BWDU12C, K_VCOPY, K_FWDT, K_BWDT, K_SWEEPF, K_SWEEPB, K_UROWS, K_FWDP, K_NKIND
-};
-inline const char* const kKindName[] = {"assemble", "small", "panel",
-                                  "trsm", "trsm", "gemm", "solve", "solve", "solve", "solve",
-                                  "solve", "solve", "gemm22", "trsm", "trsm", "gemmu", "gemmo", "trsm", "solve", "solve",
-                                  "solve", "solve", "solve", "solve", "urows", "solve"};
-static_assert(sizeof(kKindName) / sizeof(kKindName[0]) == K_NKIND, "one kKindName entry per launch kind");
-constexpr int kSolveBigNs = 256;  // fronts with more pivots use the multi-workgroup solve
-// ... and so do fronts whose L panel (M x ns entries) exceeds this: one workgroup streams a
-// tall panel at single-CU bandwidth (a 10^4-row front with 200 pivots took ~350 us per sweep)
-constexpr int64_t kSolveBigWork = 1 << 16;
-constexpr int kSolveMicroM = 8;    // tiny fronts with M <= 8: eight per wave (k_fwd_micro / k_bwd_micro)
-constexpr int kSolveTinyM = 128;   // fronts with M <= 128 rows and ns <= 64: one wave each (k_fwd_tiny / k_bwd_tiny)
-
-struct Launch {
-  int kind = 0;
-  int node = 0;                           // K_BWDU12C / K_VCOPY: front or block node
-  int step = 0;
-  int64_t off = 0, cnt = 0, nwg = 0, aux = 0, aux2 = 0;
-  int64_t off2 = 0, cnt2 = 0, nwg2 = 0;   // second work list (merged launches)
-  double flops = 0;
-  // solves (one GPU): consecutive launches with the same grp > 0 are one level's fronts; in batched
-  // solves (the per-block schedule) the side ones (small and tiny fronts) run on the handle's side
-  // stream next to the large fronts' chain
-  int grp = 0;
-  bool side = false;
-};
 
 template <class T>
 struct DBuf {
@@ -147,44 +111,6 @@ struct DBuf {
     if (p) (void)hipFree(p);
     p = nullptr;
     n = 0;
-  }
-};
-
-// Host description of one copy of a pack / unpack step, resolved to device addresses once the
-// buffers exist: base 0 store, 1 scratch, 2 vbuf, 3 wrk (x), 4 send staging, 5 receive staging,
-// 6 broadcast block buffer, 7 tile inverses, 8 swap lists, 9 rowperm; offsets in bytes.
-struct HSeg {
-  int sb;
-  int64_t so;
-  int db;
-  int64_t dof;
-  int64_t bytes;
-};
-
-// One communication step between segments of the schedule.
-struct CommOp {
-  int type = 0;                          // 0: exchange with peers, 1: broadcast within a group
-  std::vector<int32_t> peer;             // exchange: peers (ascending)
-  std::vector<int> sbase, rbase;         // per peer: buffer (HSeg base ids) and byte offsets
-  std::vector<int64_t> soff, roff, sbytes, rbytes;
-  int32_t root = -1;                     // broadcast: root and group (ascending, includes root)
-  std::vector<int32_t> grp;
-  int bbase = 4;                         // broadcast buffer: send staging on the root, the
-  int64_t bytes = 0;                     //   block buffer elsewhere
-  std::vector<HSeg> pack, unpack;        // copies before / after the transfer
-  int64_t pack0 = 0, unpack0 = 0;        // ranges in the device descriptor array
-  // per-peer helpers used while the schedule is built
-  int at(int32_t p) {
-    for (size_t i = 0; i < peer.size(); ++i)
-      if (peer[i] == p) return (int)i;
-    peer.push_back(p);
-    sbase.push_back(4);
-    rbase.push_back(5);
-    soff.push_back(0);
-    roff.push_back(0);
-    sbytes.push_back(0);
-    rbytes.push_back(0);
-    return (int)peer.size() - 1;
   }
 };
 
@@ -264,21 +190,11 @@ struct smlu_handle {
   DBuf<int32_t> ssync, sstatus;   // sync-free solve sweeps: block flags (epochs, never reset); timeouts
   DBuf<unsigned long long> stick; // ... one monotone ticket counter per sweep launch
   DBuf<double> sxh;               // ... hand-off slots: 64 x kMultiRhs doubles per flag
-  int64_t ssync_n = 0;
   DBuf<GemmTask> gtasks;
   DBuf<SwapTask> stasks;
   DBuf<URowTask> urtasks;     // fused U-row tasks (k_urows)
   DBuf<XCol> xcols;
-  // schedule
-  std::vector<Launch> fac, fwd, bwd;
-  std::vector<Launch> fwdm, bwdm;   // per-block launches instead of sweeps: batched right-hand sides (one
-                                    // GPU) and the re-run of a solve whose sweep wait timed out
-  std::vector<size_t> fwdm_seg, bwdm_seg;   // their segment starts (the comm steps of fwd / bwd)
-  std::vector<SNode> hsn;
-  double gemm_flops = 0, gemm22_flops = 0, dense_flops = 0;
-  int64_t gemm_launches = 0, gemm128_launches = 0;
-  double gemm_bytes = 0;      // algorithmic bytes of the GEMM launches: A, B read, C read + written
-  int64_t nlaunch = 0;
+  Schedule sch;   // the static schedule (schedule_build.cpp); its work lists are dropped once uploaded
   // stats
   double refactor_ms = 0, solve_ms = 0, growth_max = 0;
   int64_t weak = 0;
@@ -305,15 +221,9 @@ struct smlu_handle {
   std::vector<hipGraphExec_t> fac_execs;   // one captured graph per factor segment
   int fac_exec_profile = -1;
   std::vector<std::pair<size_t, size_t>> seg_events;   // profile events of each captured segment
-  // multi-GPU partition (smlu_dist_*): this rank's fronts and column blocks (RankLayout), the
-  // schedule cut into segments at the communication steps
+  // multi-GPU partition (smlu_dist_*): this rank's fronts and column blocks (RankLayout)
   int rank = 0, nranks = 1;
   RankLayout lay;
-  int64_t nnodes = 0;                              // fronts + block nodes of shared fronts
-  std::vector<int32_t> node_front;                 // node -> front
-  std::vector<size_t> fac_seg, fwd_seg, bwd_seg;   // launch index where each segment starts
-  std::vector<int> fac_comm, fwd_comm, bwd_comm;   // comm op run before segment k >= 1
-  std::vector<CommOp> comm;
   smlu_transport tr{};
   void* rccl = nullptr;                            // built-in RCCL transport state
   DBuf<double> stage_s, stage_r, bcbuf, d_red;
@@ -326,11 +236,6 @@ struct smlu_handle {
   int64_t comm_calls = 0;
   size_t fac_graph_events = 0;
   bool graph_failed = false;
-  bool host_only = false;      // schedule built without a device (smlu_plan_rank_schedule)
-  double host_bytes[5] = {0};  // ... and the bytes it would allocate (build_schedule_host)
-  int ob = kOBDefault;        // outer block width (SMLU_OB overrides; multiple of 64)
-  int64_t t128_min = 512;     // 128x128 GEMM tiles when a launch has at least this many
-  bool small_k = true;        // k <= 64 launches use k_gemm_k64 (SMLU_SMALLK=0: off)
   bool dominant = false;      // A diagonally dominant (by rows or columns): last host values seen
   int pivmode = 0;            // 0: diagonal-tile pivoting for large (and, if dominant, mid-size)
                               //    fronts; 1: full-candidate pivoting in every blocked front (the
@@ -344,7 +249,6 @@ struct smlu_handle {
   int32_t repivot_info = 0;   //   word (bit 0 zero pivot, bit 1 weak pivot) and the growth seen
   double repivot_growth = 0;
   SNode repivot_sn{};         //   and that node's record (mode, ns, nu) in the schedule that flagged it
-  bool trsm_gemm = true;      // GEMM-form triangular solves of the blocked fronts
   // ComplexF64 handle (smlu_create_z): the plan and factors are those of the real-equivalent K
   bool zc = false;
   bool cpair = false;                // pair-preserving pivots (complex handle, no row transversal)
@@ -536,7 +440,7 @@ int create_impl(int64_t n, const int64_t* colptr, const int64_t* rowval, const d
 std::vector<int64_t> diagonal_match(int64_t n, const int64_t* colptr, const int64_t* rowval, const double* a,
                                     int64_t base);   // smlu.cpp
 int setup_device(smlu_handle* h);                        // schedule.cpp
-int build_schedule_host(smlu_handle* h);
+void schedule_bytes(const Plan& P, const RankLayout& lay, const Schedule& S, int rank, int nranks, double out[5]);
 int rebuild_schedule(smlu_handle* h);
 bool has_tile_fronts(const smlu_handle* h);
 int run_factor(smlu_handle* h, bool redecide = false);   // factor.cpp

@@ -89,8 +89,8 @@ int create_impl(int64_t n, const int64_t* colptr, const int64_t* rowval, const d
   h->cpair = preorder != nullptr && !h->plan.matched;
   if (!p && !h->plan.matched) h->dominant = diagonally_dominant(n, colptr, rowval, nzval, h->opts.index_base);
   if (nranks > 1) {
-    if (tune().ob > 0) h->ob = tune().ob;
-    h->plan.compute_owners(nranks, h->ob);
+    if (tune().ob > 0) h->sch.ob = tune().ob;
+    h->plan.compute_owners(nranks, h->sch.ob);
     h->opts.profile = 0;   // per-kind event timing is single-GPU only
   }
   rc = setup_device(h.get());
@@ -199,7 +199,7 @@ double smlu_stat(const smlu_handle* h, const char* key) {
   std::string k(key);
   if (k == "complex") return h->zc ? 1.0 : 0.0;
   if (k == "cpair") return h->cpair ? 1.0 : 0.0;
-  if (k == "launches") return (double)h->nlaunch;
+  if (k == "launches") return (double)h->sch.nlaunch;
   if (k == "refactor_ms_last") return h->refactor_ms;
   if (k == "solve_ms_last") return h->solve_ms;
   if (k == "growth_max") return h->growth_max;
@@ -209,7 +209,7 @@ double smlu_stat(const smlu_handle* h, const char* key) {
   if (k == "matched") return h->plan.matched ? 1.0 : 0.0;
   if (k == "nranks") return (double)h->nranks;
   if (k == "owned_blocks") return (double)h->lay.blocks.size();
-  if (k == "comm_steps") return (double)h->comm.size();
+  if (k == "comm_steps") return (double)h->sch.comm.size();
   if (k == "comm_calls") return (double)h->comm_calls;
   if (k == "comm_bytes_sent") return h->comm_sent;
   if (k == "comm_bytes_recv") return h->comm_recv;
@@ -246,14 +246,14 @@ double smlu_stat(const smlu_handle* h, const char* key) {
   }
   if (k == "solve_sweeps") {
     int64_t c = 0;
-    for (const Launch& L : h->fwd) c += L.kind == K_SWEEPF;
-    for (const Launch& L : h->bwd) c += L.kind == K_SWEEPB;
+    for (const Launch& L : h->sch.fwd) c += L.kind == K_SWEEPF;
+    for (const Launch& L : h->sch.bwd) c += L.kind == K_SWEEPB;
     return (double)c;
   }
   if (k.rfind("launches_", 0) == 0) {   // launches per kernel variant in the factor schedule
     const std::string v = k.substr(9);
     double c = 0;
-    for (const Launch& L : h->fac) {
+    for (const Launch& L : h->sch.fac) {
       const bool gemm = L.kind == K_GEMM || L.kind == K_GEMMU || L.kind == K_GEMMO || L.kind == K_GEMM22;
       const bool trsm = L.kind == K_TRSML;
       const bool mfma = L.aux == 131 || L.aux == 135;
@@ -272,7 +272,7 @@ double smlu_stat(const smlu_handle* h, const char* key) {
   if (k.rfind("fronts_mode", 0) == 0) {
     const int m = std::atoi(k.c_str() + 11);
     double c = 0;
-    for (const SNode& r : h->hsn) c += r.mode == m ? 1 : 0;
+    for (const SNode& r : h->sch.hsn) c += r.mode == m ? 1 : 0;
     return c;
   }
   if (k == "pattern_dropped") return (double)h->pattern_dropped;
@@ -284,11 +284,11 @@ double smlu_stat(const smlu_handle* h, const char* key) {
   if (k == "refine_steps") return (double)h->refine_steps;
   if (k == "refine_residual") return h->refine_resid;
   if (k == "refine_berr") return h->refine_berr;
-  if (k == "gemm_flops") return h->gemm_flops;
-  if (k == "gemm22_flops") return h->gemm22_flops;
-  if (k == "gemm_launches") return (double)h->gemm_launches;
-  if (k == "gemm_bytes") return h->gemm_bytes;
-  if (k == "gemm128_launches") return (double)h->gemm128_launches;
+  if (k == "gemm_flops") return h->sch.gemm_flops;
+  if (k == "gemm22_flops") return h->sch.gemm22_flops;
+  if (k == "gemm_launches") return (double)h->sch.gemm_launches;
+  if (k == "gemm_bytes") return h->sch.gemm_bytes;
+  if (k == "gemm128_launches") return (double)h->sch.gemm128_launches;
   if (k == "vendor_calls") return 0.0;   // no vendor GEMM path (round 5)
   if (k.rfind("ms_", 0) == 0) {
     std::string name = k.substr(3);
@@ -378,7 +378,7 @@ int smlu_get_fronts(smlu_handle* h, int64_t* first, int64_t* parent, int64_t* ro
   if (!h) return fail(h, SMLU_ERR_ARG, "NULL handle");
   fronts_of(h->plan, first, parent, rowptr, rows, p0);
   if (mode)
-    for (int64_t s = 0; s < h->plan.nsup; ++s) mode[s] = h->hsn[s].mode;
+    for (int64_t s = 0; s < h->plan.nsup; ++s) mode[s] = h->sch.hsn[s].mode;
   return SMLU_OK;
 }
 

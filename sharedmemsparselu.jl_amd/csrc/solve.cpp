@@ -37,10 +37,10 @@ static hipError_t run_solve_launch(smlu_handle* h, const Launch& L, double* w, d
                               h->ssync.p + L.aux, h->sxh.p + L.aux * 64 * kMultiRhs, h->sstatus.p, h->sn.p, h->store.p,
                               w, v, rh, h->sweep_spin);
     case K_BWDU12C:
-      return launch_bwd_u12_cols(st, h->sn.p, L.node, h->hsn[L.node].ns, L.aux, L.aux2, (int)L.cnt, h->rows.p,
+      return launch_bwd_u12_cols(st, h->sn.p, L.node, h->sch.hsn[L.node].ns, L.aux, L.aux2, (int)L.cnt, h->rows.p,
                                  h->store.p, w, h->vbuf.p);
     case K_VCOPY:
-      return launch_vcopy(st, h->sn.p, L.node, h->hsn[L.node].ns, w, h->vbuf.p);
+      return launch_vcopy(st, h->sn.p, L.node, h->sch.hsn[L.node].ns, w, h->vbuf.p);
   }
   return hipErrorInvalidValue;
 }
@@ -78,7 +78,7 @@ static int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode,
   // after every solve that ran them; the solve is then re-run on the per-block schedule (fwdm / bwdm,
   // bitwise the same arithmetic), so a timed-out sweep never returns a wrong x.  Partitioned handles
   // agree on the re-run (allreduce of the flag: the per-block sequences hold the same comm steps).
-  const bool check = !steps && (h->ssync_n > 0 || h->nranks > 1);
+  const bool check = !steps && (h->sch.ssync_n > 0 || h->nranks > 1);
   const double* src = mode == 0 ? db : dx;
   const int64_t lds = mode == 0 && ldb > 0 ? ldb : P.n;
   auto load_input = [&](const double* in, int64_t ld) -> hipError_t {
@@ -132,11 +132,11 @@ static int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode,
   };
   auto sweeps = [&](bool steps) {   // steps: the per-block sequences instead of the sweeps
     if (mode != 2) {
-      int rc = steps ? run_seq(h->fwdm, h->fwdm_seg, h->fwd_comm, true) : run_seq(h->fwd, h->fwd_seg, h->fwd_comm, false);
+      int rc = steps ? run_seq(h->sch.fwdm, h->sch.fwdm_seg, h->sch.fwd_comm, true) : run_seq(h->sch.fwd, h->sch.fwd_seg, h->sch.fwd_comm, false);
       if (rc != SMLU_OK) return rc;
     }
     if (mode != 1) {
-      int rc = steps ? run_seq(h->bwdm, h->bwdm_seg, h->bwd_comm, true) : run_seq(h->bwd, h->bwd_seg, h->bwd_comm, false);
+      int rc = steps ? run_seq(h->sch.bwdm, h->sch.bwdm_seg, h->sch.bwd_comm, true) : run_seq(h->sch.bwd, h->sch.bwd_seg, h->sch.bwd_comm, false);
       if (rc != SMLU_OK) return rc;
     }
     return (int)SMLU_OK;

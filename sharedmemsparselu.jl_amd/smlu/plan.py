@@ -128,6 +128,17 @@ class Plan:
                 "owned_blocks": int(cn[2])}
         return steps, info
 
+    def schedule_digest(self, nparts=1, rank=0, flags=0):
+        """Section hashes of rank `rank`'s schedule (smlu_plan_schedule_digest) as a uint64 array;
+        flags: 1 not dominant, 2 pivmode 1, 4 pair-preserving pivots, 8 no MFMA."""
+        n = ctypes.c_int64()
+        out = np.zeros(256, np.uint64)
+        rc = C.lib().smlu_plan_schedule_digest(self._h, int(nparts), int(rank), int(flags), C.ptr(out), out.size,
+                                               ctypes.byref(n))
+        if rc != 0:
+            raise RuntimeError(f"smlu_plan_schedule_digest failed ({rc}): {C.last_error(None)}")
+        return out[:n.value].copy()
+
     def project(self, nparts, tflops=52.0, gbs=100.0, lat_us=20.0):
         """Projected partitioned factorization time (s) and the one-GPU time of the same model."""
         t1 = ctypes.c_double()

@@ -1,6 +1,7 @@
 // Host AddressSanitizer / UBSan driver (SURVEY §5 "race detection / sanitizers": host side).
 // Builds the host symbolic plan (csrc/plan.cpp, ordering.cpp, amd.cpp) for several inputs and
-// every ordering, the multi-GPU partition, per-rank layouts and the projection, and runs the CPU
+// every ordering, the multi-GPU partition, per-rank layouts, every rank's schedule
+// (csrc/schedule_build.cpp) and the projection, and runs the CPU
 // oracle (oracle/oracle.c fixed-pivot LU + solves, oracle/mf.c multifrontal pivot-choosing LU) on
 // the plan's assembly tree -- all under -fsanitize=address,undefined (tools/sanitize/Makefile).
 // No GPU code is compiled: device kernels cannot run under the sanitizers on this pool.
@@ -13,6 +14,7 @@
 
 #include "../../oracle/oracle.h"
 #include "../../sharedmemsparselu.jl_amd/csrc/plan.hpp"
+#include "../../sharedmemsparselu.jl_amd/csrc/schedule.hpp"
 
 using namespace smlu;
 
@@ -76,7 +78,40 @@ static int check(bool ok, const char* what) {
   return ok ? 0 : 1;
 }
 
-static int run_case(const char* name, const Csc& A, int ordering, const int64_t* grid, bool dominant = true) {
+// Every launch's [off, off + cnt) inside the array its kind indexes (ilist entries come in groups
+// of 3 per small front, 2 per panel / tile inverse, 1 per solve front).
+static bool launches_in_range(const Schedule& S) {
+  const std::vector<Launch>* seqs[5] = {&S.fac, &S.fwd, &S.bwd, &S.fwdm, &S.bwdm};
+  auto in = [](int64_t off, int64_t n, size_t size) { return off >= 0 && n >= 0 && off + n <= (int64_t)size; };
+  for (const auto* seq : seqs)
+    for (const Launch& L : *seq) {
+      bool ok = false;
+      switch (L.kind) {
+        case K_EXTADD: ok = in(L.off, L.cnt, S.xc.size()); break;
+        case K_FRONT_LDS: ok = in(L.off, 3 * L.cnt, S.ilist.size()); break;
+        case K_PANEL: case K_TRIINV: ok = in(L.off, 2 * L.cnt, S.ilist.size()); break;
+        case K_FWD: case K_BWD: case K_FWDT: case K_BWDT: case K_FWDG: ok = in(L.off, L.cnt, S.ilist.size()); break;
+        case K_LASWP: ok = in(L.off, L.cnt, S.st_tasks.size()); break;
+        case K_STEPTRSM: ok = in(L.off, L.cnt, S.ft.size()) && in(L.off2, L.cnt2, S.ft.size()); break;
+        case K_TRSMU: case K_FWDP: case K_BWDU: case K_SWEEPF: case K_SWEEPB: case K_TRIF: case K_TRIB:
+          ok = in(L.off, L.cnt, S.ft.size());
+          break;
+        case K_TRSML: case K_GEMM: case K_GEMM22: case K_GEMMU: case K_GEMMO: ok = in(L.off, L.cnt, S.gt.size()); break;
+        case K_UROWS: ok = in(L.off, L.cnt, S.ur_tasks.size()); break;
+        case K_BWDU12C: case K_VCOPY: ok = L.node >= 0 && L.node < S.nnodes; break;
+        default: ok = false;
+      }
+      if (!ok) {
+        std::fprintf(stderr, "launch kind %d: [%lld, +%lld) out of range\n", L.kind, (long long)L.off, (long long)L.cnt);
+        return false;
+      }
+    }
+  return true;
+}
+
+// oracle = false: the plan, the partition and the schedules only, and the partition must share fronts
+static int run_case(const char* name, const Csc& A, int ordering, const int64_t* grid, bool dominant = true,
+                    bool oracle = true) {
   int bad = 0;
   PlanOptions o;
   o.ordering = ordering;
@@ -94,6 +129,7 @@ static int run_case(const char* name, const Csc& A, int ordering, const int64_t*
     std::fprintf(stderr, "%s: plan failed: %s\n", name, e.c_str());
     return 1;
   }
+  int64_t bcasts = 0;   // pivot-block broadcasts: the shared-front chains were scheduled
   for (int np : {1, 2, 3, 8}) {
     P.compute_owners(np, 384);
     double t1 = 0;
@@ -103,7 +139,26 @@ static int run_case(const char* name, const Csc& A, int ordering, const int64_t*
       RankLayout L;
       rank_layout(P, r, L);
       bad += check(L.store_size >= 0 && L.scratch_size >= 0, "rank layout sizes");
+      rank_layout_of(P, r, np, L);   // the layout a handle uses (one GPU: the plan's own)
+      for (int flags : {0, 1}) {   // dominant values (diagonal-tile panels) / not (full-candidate panels)
+        ScheduleInput in;
+        in.plan = &P;
+        in.lay = &L;
+        in.rank = r;
+        in.nranks = np;
+        in.dominant = flags == 0;
+        Schedule S;
+        const std::string se = build_schedule(in, S);
+        bad += check(se.empty(), "schedule builds");
+        bad += check(se.empty() && launches_in_range(S), "launch ranges");
+        for (const CommOp& op : S.comm) bcasts += op.type == 1;
+      }
     }
+  }
+  if (!oracle) {
+    bad += check(bcasts > 0, "shared fronts scheduled");
+    std::printf("%-28s n=%-6lld nsup=%-6lld ok=%d\n", name, (long long)A.n, (long long)P.nsup, bad == 0);
+    return bad;
   }
   // oracle: multifrontal pivot-choosing LU on the plan's tree, then the fixed-pivot LU with its p
   std::vector<int64_t> first(P.s_first.begin(), P.s_first.end()), parent(P.s_parent.begin(), P.s_parent.end()),
@@ -154,6 +209,8 @@ int main() {
   bad += run_case("random_small_diag_300", random_sparse(300, 0.03, false, 5), 0, nullptr, false);
   bad += run_case("poisson3d_3", poisson3d(3), 0, nullptr);
   bad += run_case("one_entry", random_sparse(1, 0.0, true, 1), 0, nullptr);
+  // large enough for shared fronts: the multi-GPU chains of every rank's schedule
+  bad += run_case("poisson3d_40 graph-nd sched", poisson3d(40), 3, nullptr, true, false);
   std::printf(bad == 0 ? "HOST SANITIZER RUN OK\n" : "HOST SANITIZER RUN FAILED\n");
   return bad == 0 ? 0 : 1;
 }
