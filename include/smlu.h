@@ -150,6 +150,28 @@ int smlu_solve_multi(smlu_handle* h, int64_t nrhs, const double* B, int64_t ldb,
 int smlu_solve_multi_device(smlu_handle* h, int64_t nrhs, const double* d_B, int64_t ldb, double* d_X,
                             int64_t ldx);
 
+/* Transposed and adjoint solves from the same factors: ldiv!(x, transpose(F), b) / ldiv!(x, F', b)
+ * (UMFPACK_At / UMFPACK_Aat, SuperLU trans = 'T' / 'H').  No second analysis or factorization and
+ * no extra factor memory: the factors of A are swept in the transposed direction.
+ *   op = SMLU_OP_N forwards to the matching smlu_solve* entry point (bitwise its result);
+ *   op = SMLU_OP_T solves A^T x = b;  op = SMLU_OP_H solves A^H x = b (a real handle: the same as T;
+ *   a ComplexF64 handle: 2n interleaved doubles, as smlu_solve);  any other op: SMLU_ERR_ARG.
+ * Conventions of smlu_solve*: x == b allowed, the _device forms are ordered after the caller's
+ * stream (smlu_set_stream), iterative refinement by the same rule (residual b - A^T x with the
+ * componentwise denominator |A^T||x| + |b|; "refine_steps" / "refine_berr"), "solve_ms_last" set.
+ * Two solves of the same b are bitwise equal.  Single-GPU only: a partitioned handle (smlu_dist_*)
+ * gives SMLU_ERR_STATE.  The _multi forms solve column by column on the single-vector path (no
+ * batched transposed kernels). */
+#define SMLU_OP_N 0   /* A x = b   */
+#define SMLU_OP_T 1   /* A^T x = b */
+#define SMLU_OP_H 2   /* A^H x = b (real handle: same as T) */
+int smlu_solve_trans(smlu_handle* h, int op, const double* b, double* x);
+int smlu_solve_trans_device(smlu_handle* h, int op, const double* d_b, double* d_x);
+int smlu_solve_trans_multi(smlu_handle* h, int op, int64_t nrhs, const double* B, int64_t ldb, double* X,
+                           int64_t ldx);
+int smlu_solve_trans_multi_device(smlu_handle* h, int op, int64_t nrhs, const double* d_B, int64_t ldb,
+                                  double* d_X, int64_t ldx);
+
 /* ParallelSparseLU(A::SparseMatrixCSC{Float64,Int32}) — Int32 index arrays;
  * converted to the Int64 path on the host. */
 int smlu_create_i32(int64_t n, const int32_t* colptr, const int32_t* rowval, const double* nzval,

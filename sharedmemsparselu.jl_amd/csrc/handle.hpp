@@ -85,6 +85,25 @@ hipError_t launch_bwd_u12_cols(hipStream_t, const SNode*, int, int64_t, int64_t,
                                const double*, const double*, double*);
 hipError_t launch_vcopy(hipStream_t, const SNode*, int, int64_t, const double*, double*);
 hipError_t launch_unswap(hipStream_t, int64_t, const int64_t*, const int32_t*, const double*, double*);
+// kernels_solve_t.hip: the transposed / adjoint solve
+hipError_t launch_ut_tiny(hipStream_t, int, const int32_t*, const SNode*, const int32_t*, const int32_t*, const double*,
+                          double*, double*, int);
+hipError_t launch_lt_tiny(hipStream_t, int, const int32_t*, const SNode*, const int32_t*, const int32_t*, const double*,
+                          double*, int);
+hipError_t launch_ut_front(hipStream_t, int, const int32_t*, const SNode*, const int32_t*, const int32_t*,
+                           const double*, double*, double*);
+hipError_t launch_lt_front(hipStream_t, int, const int32_t*, const SNode*, const int32_t*, const int32_t*,
+                           const double*, double*, double*);
+hipError_t launch_pull_t(hipStream_t, int64_t, const FrontTile*, int, const SNode*, const int32_t*, const int32_t*,
+                         const double*, double*);
+hipError_t launch_tri_t(hipStream_t, bool, int64_t, const FrontTile*, int, int, const SNode*, const int32_t*,
+                        const double*, double*, double*);
+hipError_t launch_bwdu_t(hipStream_t, int64_t, const FrontTile*, int, const SNode*, const int32_t*, const double*,
+                         const double*, double*);
+hipError_t launch_perm_in_t(hipStream_t, int64_t, const int64_t*, const double*, double*, int);
+hipError_t launch_perm_out_t(hipStream_t, int64_t, const int64_t*, const double*, const double*, double*, int);
+hipError_t launch_residual_t(hipStream_t, int64_t, const int64_t*, const int32_t*, const double*, const double*,
+                             const double*, double*, double*, int);
 }  // namespace smlu
 
 using namespace smlu;

@@ -392,6 +392,241 @@ int smlu_solve_multi(smlu_handle* h, int64_t nrhs, const double* B, int64_t ldb,
   return SMLU_OK;
 }
 
+// ---- transposed / adjoint solves: A^T x = b, A^H x = b from the factors of A -------------------
+// (Rs .* A)[p0, q] = P_fronts^T L U, so A^T x = b is w = b[q]; U^T y = w, leaves -> root; the L^T and
+// front-permutation pass root -> leaves; x[p0] = Rs[p0] .* z (kernels_solve_t.hip).  The two passes
+// walk the per-block sequences fwdm / bwdm, which every one-GPU handle has, and reinterpret each
+// launch by kind on the same work lists and workgroup counts; the schedule itself is untouched.
+// A ComplexF64 handle's K^T is the real equivalent of A^H: the same passes give the adjoint solve,
+// and the plain transpose is conj(A^H \ conj(b)), the conjugations folded into the permutations.
+static hipError_t run_solve_launch_t(smlu_handle* h, const Launch& L, double* w, double* v, hipStream_t st) {
+  switch (L.kind) {
+    case K_FWDT:
+      return launch_ut_tiny(st, (int)L.cnt, h->ilist.p + L.off, h->sn.p, h->chlist.p, h->relmap.p, h->store.p, w, v,
+                            (int)L.aux);
+    case K_FWD:
+      return launch_ut_front(st, (int)L.cnt, h->ilist.p + L.off, h->sn.p, h->chlist.p, h->relmap.p, h->store.p, w, v);
+    case K_FWDP:
+      return launch_pull_t(st, L.nwg, h->ftiles.p + L.off, (int)L.cnt, h->sn.p, h->gptr.p, h->gent.p, w, v);
+    case K_TRIF:
+      return launch_tri_t(st, false, L.nwg, h->ftiles.p + L.off, (int)L.cnt, L.step, h->sn.p, h->rowperm.p,
+                          h->store.p, w, v);
+    case K_BWDT:
+      return launch_lt_tiny(st, (int)L.cnt, h->ilist.p + L.off, h->sn.p, h->rows.p, h->rowperm.p, h->store.p, w,
+                            (int)L.aux);
+    case K_BWD:
+      return launch_lt_front(st, (int)L.cnt, h->ilist.p + L.off, h->sn.p, h->rows.p, h->rowperm.p, h->store.p, w, v);
+    case K_BWDU:
+      return launch_bwdu_t(st, L.nwg, h->ftiles.p + L.off, (int)L.cnt, h->sn.p, h->rows.p, h->store.p, w, v);
+    case K_TRIB:
+      return launch_tri_t(st, true, L.nwg, h->ftiles.p + L.off, (int)L.cnt, L.step, h->sn.p, h->rowperm.p,
+                          h->store.p, w, v);
+  }
+  return hipErrorInvalidValue;   // no transposed meaning (the sequences of a one-GPU handle hold none)
+}
+
+constexpr int kTransGraphKey = 1 << 12;   // sol_execs key of the transposed passes (forward: mode * 256 + rhs)
+
+static int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* dx) {
+  Plan& P = h->plan;
+  hipStream_t st = h->stream;
+  auto t0 = std::chrono::steady_clock::now();
+  Timer tm(h);
+  hipEvent_t stop;
+  HIPCHK(tm.begin(K_FWD, &stop, st));
+  double* w = h->wrk.p;
+  double* v = h->vbuf.p;
+  HIPCHK(launch_perm_in_t(st, P.n, h->q.p, db, w, conj));
+  // a level's side launches on the side stream, forked after everything before the level and joined
+  // before the next level -- and on the error path, so a failed launch never leaves the side stream
+  // unjoined (inside a capture that would invalidate it)
+  auto run_seq = [&](const std::vector<Launch>& seq) {
+    bool forked = false;
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; i < seq.size() && e == hipSuccess; ++i) {
+      const Launch& L = seq[i];
+      const bool first = L.grp > 0 && (i == 0 || seq[i - 1].grp != L.grp);
+      const bool last = L.grp > 0 && (i + 1 == seq.size() || seq[i + 1].grp != L.grp);
+      if (first) {
+        e = hipEventRecord(h->fork_ev, st);
+        if (e == hipSuccess) e = hipStreamWaitEvent(h->side, h->fork_ev, 0);
+        forked = e == hipSuccess;
+      }
+      if (e == hipSuccess) e = run_solve_launch_t(h, L, w, v, L.side && forked ? h->side : st);
+      if (e == hipSuccess && last && forked) {
+        e = hipEventRecord(h->join_ev, h->side);
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, h->join_ev, 0);
+        if (e == hipSuccess) forked = false;
+      }
+    }
+    if (forked) {
+      (void)hipEventRecord(h->join_ev, h->side);
+      (void)hipStreamWaitEvent(st, h->join_ev, 0);
+    }
+    if (e != hipSuccess) return fail(h, SMLU_ERR_HIP, std::string("HIP error: ") + hipGetErrorString(e) + " in the transposed solve");
+    return (int)SMLU_OK;
+  };
+  auto passes = [&]() {
+    int rc = run_seq(h->sch.fwdm);
+    return rc != SMLU_OK ? rc : run_seq(h->sch.bwdm);
+  };
+  // the two passes (fixed pointers: the handle's wrk / vbuf) captured once into a hipGraph and replayed
+  hipGraphExec_t ex = nullptr;
+  if (!tune().no_graph && !h->graph_failed) {
+    for (auto& g : h->sol_execs)
+      if (g.first == kTransGraphKey) ex = g.second;
+    if (!ex) {
+      hipGraph_t g = nullptr;
+      HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+      int rc = passes();
+      hipError_t ec = hipStreamEndCapture(st, &g);
+      if (rc == SMLU_OK && ec == hipSuccess && g) ec = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+      if (g) (void)hipGraphDestroy(g);
+      if (rc != SMLU_OK || ec != hipSuccess || !ex) {
+        (void)hipGetLastError();
+        h->graph_failed = true;
+        ex = nullptr;
+      } else {
+        h->sol_execs.push_back({kTransGraphKey, ex});
+      }
+    }
+  }
+  if (ex) HIPCHK(hipGraphLaunch(ex, st));
+  else {
+    int rc = passes();
+    if (rc != SMLU_OK) return rc;
+  }
+  HIPCHK(launch_perm_out_t(st, P.n, h->p0.p, h->Rs.p, w, dx, conj));
+  HIPCHK(tm.end(stop));
+  HIPCHK(hipStreamSynchronize(st));
+  tm.collect();
+  h->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return SMLU_OK;
+}
+
+// The transposed solve with solve_refined's refinement rule: r = b - A^T x by columns of A's CSC,
+// componentwise denominator |A^T||x| + |b|, same stop test and the same refine_* stats.
+static int solve_refined_t(smlu_handle* h, int conj, const double* db, double* dx) {
+  const int steps = auto_refine_steps(h);
+  h->refine_steps = 0;
+  h->refine_resid = -1;
+  h->refine_berr = -1;
+  if (steps == 0) return run_solve_t_dev(h, conj, db, dx);
+  Plan& P = h->plan;
+  const int64_t n = P.n;
+  hipStream_t st = h->stream;
+  int rc0 = ensure_residual(h);
+  if (rc0 != SMLU_OK) return rc0;
+  if (!h->Acolp.p) HIPCHK(h->Acolp.upload(P.Acolptr.data(), P.Acolptr.size(), st));
+  HIPCHK(hipMemcpyAsync(h->ref_b.p, db, sizeof(double) * n, hipMemcpyDeviceToDevice, st));   // db may alias dx
+  int rc = run_solve_t_dev(h, conj, h->ref_b.p, dx);
+  if (rc != SMLU_OK) return rc;
+  const double ms = h->solve_ms;
+  const double eps = std::ldexp(1.0, -51);   // 4 unit roundoffs
+  double prev = HUGE_VAL;
+  for (int it = 0; it < steps; ++it) {
+    HIPCHK(hipMemsetAsync(h->ref_nrm.p, 0, 2 * sizeof(double), st));
+    HIPCHK(launch_residual_t(st, n, h->Acolp.p, h->Arow.p, h->A.p, dx, h->ref_b.p, h->ref_r.p, h->ref_nrm.p, conj));
+    long long rec[16];
+    rc = read_status(h, nullptr, 0, reinterpret_cast<const int32_t*>(h->ref_nrm.p), 4, rec);
+    if (rc != SMLU_OK) return rc;
+    double nrm, berr;
+    std::memcpy(&nrm, &rec[6], sizeof nrm);
+    std::memcpy(&berr, &rec[7], sizeof berr);
+    h->refine_resid = nrm;
+    h->refine_berr = berr;
+    if (berr <= eps || berr > 0.5 * prev) break;
+    prev = berr;
+    rc = run_solve_t_dev(h, conj, h->ref_r.p, h->ref_d.p);
+    if (rc != SMLU_OK) return rc;
+    HIPCHK(launch_axpy1(st, n, h->ref_d.p, dx));
+    ++h->refine_steps;
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  h->solve_ms = ms;   // the plain solve's time (refinement steps reported separately)
+  return SMLU_OK;
+}
+
+// op and handle checks shared by the four entry points; *conj: conjugate in and out
+static int trans_check(smlu_handle* h, int op, int* conj) {
+  if (op != SMLU_OP_T && op != SMLU_OP_H) return fail(h, SMLU_ERR_ARG, "op must be SMLU_OP_N, SMLU_OP_T or SMLU_OP_H");
+  if (!h->have_numeric) return fail(h, SMLU_ERR_STATE, "no numeric factorization");
+  if (h->nranks > 1) return fail(h, SMLU_ERR_STATE, "transposed solves are single-GPU only");
+  *conj = h->zc && op == SMLU_OP_T;
+  return SMLU_OK;
+}
+
+int smlu_solve_trans_device(smlu_handle* h, int op, const double* d_b, double* d_x) {
+  if (!h || !d_b || !d_x) return fail(h, SMLU_ERR_ARG, "NULL argument");
+  if (op == SMLU_OP_N) return smlu_solve_device(h, d_b, d_x);
+  int conj = 0;
+  int rc = trans_check(h, op, &conj);
+  if (rc != SMLU_OK) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(after_caller(h));
+  return solve_refined_t(h, conj, d_b, d_x);
+}
+
+int smlu_solve_trans(smlu_handle* h, int op, const double* b, double* x) {
+  if (!h || !b || !x) return fail(h, SMLU_ERR_ARG, "NULL argument");
+  if (op == SMLU_OP_N) return smlu_solve(h, b, x);
+  int conj = 0;
+  int rc = trans_check(h, op, &conj);
+  if (rc != SMLU_OK) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  const int64_t n = h->plan.n;
+  HIPCHK(hipMemcpyAsync(h->wrk2.p, b, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+  rc = solve_refined_t(h, conj, h->wrk2.p, h->wrk2.p);
+  if (rc != SMLU_OK) return rc;
+  HIPCHK(hipMemcpyAsync(x, h->wrk2.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return SMLU_OK;
+}
+
+// Several right-hand sides: one transposed solve per column (no batched transposed kernels).
+int smlu_solve_trans_multi_device(smlu_handle* h, int op, int64_t nrhs, const double* d_B, int64_t ldb, double* d_X,
+                                  int64_t ldx) {
+  if (!h || nrhs < 0 || (nrhs > 0 && (!d_B || !d_X))) return fail(h, SMLU_ERR_ARG, "invalid arguments");
+  if (op == SMLU_OP_N) return smlu_solve_multi_device(h, nrhs, d_B, ldb, d_X, ldx);
+  int conj = 0;
+  int rc = trans_check(h, op, &conj);
+  if (rc != SMLU_OK) return rc;
+  const int64_t n = h->plan.n;
+  if (ldb < n || ldx < n) return fail(h, SMLU_ERR_ARG, "leading dimension smaller than n");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(after_caller(h));
+  double ms = 0;
+  for (int64_t j = 0; j < nrhs; ++j) {
+    rc = solve_refined_t(h, conj, d_B + j * ldb, d_X + j * ldx);
+    if (rc != SMLU_OK) return rc;
+    ms += h->solve_ms;
+  }
+  if (nrhs > 0) h->solve_ms = ms;
+  return SMLU_OK;
+}
+
+int smlu_solve_trans_multi(smlu_handle* h, int op, int64_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx) {
+  if (!h || nrhs < 0 || (nrhs > 0 && (!B || !X))) return fail(h, SMLU_ERR_ARG, "invalid arguments");
+  if (op == SMLU_OP_N) return smlu_solve_multi(h, nrhs, B, ldb, X, ldx);
+  int conj = 0;
+  int rc = trans_check(h, op, &conj);
+  if (rc != SMLU_OK) return rc;
+  const int64_t n = h->plan.n;
+  if (ldb < n || ldx < n) return fail(h, SMLU_ERR_ARG, "leading dimension smaller than n");
+  HIPCHK(hipSetDevice(h->device));
+  double ms = 0;
+  for (int64_t j = 0; j < nrhs; ++j) {
+    HIPCHK(hipMemcpyAsync(h->wrk2.p, B + j * ldb, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+    rc = solve_refined_t(h, conj, h->wrk2.p, h->wrk2.p);
+    if (rc != SMLU_OK) return rc;
+    ms += h->solve_ms;
+    HIPCHK(hipMemcpyAsync(X + j * ldx, h->wrk2.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (nrhs > 0) h->solve_ms = ms;
+  return SMLU_OK;
+}
+
 static int tri_solve_host(smlu_handle* h, double* x, int mode) {
   if (!h || !x) return fail(h, SMLU_ERR_ARG, "NULL argument");
   if (!h->have_numeric) return fail(h, SMLU_ERR_STATE, "no numeric factorization");

@@ -156,6 +156,36 @@ function ldiv!(x::AbstractVecOrMat, F::ParallelSparseLU{Tf}, b::AbstractVecOrMat
     return x
 end
 
+# transpose(F) \ b and F' \ b from the same factors (UMFPACK_At / UMFPACK_Aat): thin wrappers, no
+# second analysis or factorization.  op: SMLU_OP_T = 1, SMLU_OP_H = 2 (include/smlu.h).
+struct TransposedLU{Tf,Ti}; parent::ParallelSparseLU{Tf,Ti}; end
+struct AdjointLU{Tf,Ti}; parent::ParallelSparseLU{Tf,Ti}; end
+Base.transpose(F::ParallelSparseLU{Tf,Ti}) where {Tf,Ti} = TransposedLU{Tf,Ti}(F)
+Base.adjoint(F::ParallelSparseLU{Tf,Ti}) where {Tf,Ti} = AdjointLU{Tf,Ti}(F)
+Base.transpose(W::TransposedLU) = W.parent
+Base.adjoint(W::AdjointLU) = W.parent
+
+function _ldiv_trans!(op::Int32, x::AbstractVecOrMat, F::ParallelSparseLU{Tf}, b::AbstractVecOrMat) where {Tf}
+    F.m == F.n || throw(DimensionMismatch("`F` is not square: F.m=$(F.m), F.n=$(F.n)"))
+    size(x, 1) == F.n || throw(DimensionMismatch("`x` does not have same size as F: length(x)=$(length(x)), F.n=$(F.n)"))
+    size(b, 1) == F.n || throw(DimensionMismatch("`b` does not have same size as F: length(b)=$(length(b)), F.n=$(F.n)"))
+    bb = b isa Array{Tf} ? b : Array{Tf}(b)
+    xx = x isa Array{Tf} ? x : similar(bb)
+    if ndims(b) == 1
+        check(ccall((:smlu_solve_trans, libsmlu), Int32, (Ptr{Cvoid}, Int32, Ptr{Tf}, Ptr{Tf}),
+                    F.handle, op, bb, xx), F.handle)
+    else                                       # several right-hand sides: column by column in the library
+        ld = (Tf === ComplexF64 ? 2 : 1) * F.n  # leading dimension in doubles
+        check(ccall((:smlu_solve_trans_multi, libsmlu), Int32,
+                    (Ptr{Cvoid}, Int32, Int64, Ptr{Tf}, Int64, Ptr{Tf}, Int64),
+                    F.handle, op, size(b, 2), bb, ld, xx, ld), F.handle)
+    end
+    xx === x || copyto!(x, xx)
+    return x
+end
+ldiv!(x::AbstractVecOrMat, W::TransposedLU, b::AbstractVecOrMat) = _ldiv_trans!(Int32(1), x, W.parent, b)
+ldiv!(x::AbstractVecOrMat, W::AdjointLU, b::AbstractVecOrMat) = _ldiv_trans!(Int32(2), x, W.parent, b)
+
 function _trisolve!(upper::Bool, F::ParallelSparseLU{Tf}, x::AbstractVector) where {Tf}
     xx = x isa Vector{Tf} ? x : Vector{Tf}(x)
     check(ccall(fnptr(upper ? :smlu_rsolve : :smlu_lsolve), Int32, (Ptr{Cvoid}, Ptr{Tf}), F.handle, xx),

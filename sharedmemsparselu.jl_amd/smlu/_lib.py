@@ -30,6 +30,11 @@ SMLU_ERR_HIP = -4
 SMLU_ERR_NODEVICE = -5
 SMLU_ERR_STATE = -6
 
+# op of the smlu_solve_trans* entry points: A x = b, A^T x = b, A^H x = b
+SMLU_OP_N = 0
+SMLU_OP_T = 1
+SMLU_OP_H = 2
+
 ORDER_AUTO, ORDER_NATURAL, ORDER_GEOMETRIC_ND, ORDER_GRAPH_ND, ORDER_GIVEN, ORDER_AMD = range(6)
 
 
@@ -72,6 +77,10 @@ SIGNATURES = {
     "smlu_residual_device": (i32, [vp, vp, vp, vp, vp]),
     "smlu_solve_multi": (i32, [vp, i64, vp, i64, vp, i64]),
     "smlu_solve_multi_device": (i32, [vp, i64, vp, i64, vp, i64]),
+    "smlu_solve_trans": (i32, [vp, i32, vp, vp]),
+    "smlu_solve_trans_device": (i32, [vp, i32, vp, vp]),
+    "smlu_solve_trans_multi": (i32, [vp, i32, i64, vp, i64, vp, i64]),
+    "smlu_solve_trans_multi_device": (i32, [vp, i32, i64, vp, i64, vp, i64]),
     "smlu_create_i32": (i32, [i64, vp, vp, vp, ctypes.POINTER(SmluOpts), ctypes.POINTER(vp)]),
     "smlu_create_z": (i32, [i64, vp, vp, vp, ctypes.POINTER(SmluOpts), ctypes.POINTER(vp)]),
     "smlu_refactor_z": (i32, [vp, vp]),

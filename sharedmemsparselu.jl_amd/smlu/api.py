@@ -5,6 +5,8 @@ Julia name                          here                          reference
 ParallelSparseLU(A, chunk_size)     ParallelSparseLU(A, cs)       :64-98
 lu!(F, A)                           lu_(F, A)                     :245-279
 ldiv!(x, F, b)                      ldiv_(x, F, b)                :286-342
+ldiv!(x, transpose(F), b)           ldiv_(x, F, b, trans="T")     (not in the reference)
+ldiv!(x, F', b)                     ldiv_(x, F, b, trans="C")     (not in the reference)
 lsolve!(F, x), rsolve!(F, x)        lsolve_(F, x), rsolve_(F, x)  :349-392
 F.L F.U F.p F.q F.Rs                F.L F.U F.p F.q F.Rs          :45-52 (0-based here)
 cleanup_ParallelSparseLU!(F)        cleanup_ParallelSparseLU_(F)  :31 (exported, undefined there)
@@ -54,6 +56,14 @@ def _csc(A):
         A = A.sorted_indices()
     A.sum_duplicates()
     return A
+
+
+def _op(trans):
+    """trans = "N" | "T" | "C" -> SMLU_OP_N / SMLU_OP_T / SMLU_OP_H (include/smlu.h)."""
+    try:
+        return {"N": C.SMLU_OP_N, "T": C.SMLU_OP_T, "C": C.SMLU_OP_H}[trans]
+    except (KeyError, TypeError):
+        raise ValueError(f'trans must be "N", "T" or "C", got {trans!r}') from None
 
 
 def _check(rc, h=None):
@@ -273,22 +283,34 @@ class ParallelSparseLU:
             raise SingularException(C.lib().smlu_last_error_col(self._h))
         return rc
 
-    def solve_device(self, d_x, d_b):
+    def solve_device(self, d_x, d_b, trans="N"):
+        """ldiv! on device vectors; trans="T" / "C": the transposed / adjoint solve from the same
+        factors (smlu_solve_trans_device)."""
+        op = _op(trans)
         px = d_x.data_ptr() if hasattr(d_x, "data_ptr") else int(d_x)
         pb = d_b.data_ptr() if hasattr(d_b, "data_ptr") else int(d_b)
         with C.caller_stream(self._h, d_b):
+            if op != C.SMLU_OP_N:
+                return _check(C.lib().smlu_solve_trans_device(self._h, op, ctypes.c_void_p(pb),
+                                                              ctypes.c_void_p(px)), self._h)
             return _check(C.lib().smlu_solve_device(self._h, ctypes.c_void_p(pb), ctypes.c_void_p(px)),
                           self._h)
 
-    def solve_multi_device(self, d_X, d_B):
+    def solve_multi_device(self, d_X, d_B, trans="N"):
         """ldiv! for several right-hand sides on the device: d_B, d_X are (nrhs, n) contiguous
         torch tensors (column r = row r, i.e. column-major n x nrhs).  One GPU: batches of up to
-        16 columns go through the solve kernels together."""
+        16 columns go through the solve kernels together.  trans="T" / "C": one transposed /
+        adjoint solve per column (smlu_solve_trans_multi_device)."""
+        op = _op(trans)
         nrhs, n = d_B.shape
         if n != self.n or tuple(d_X.shape) != (nrhs, n):
             raise DimensionMismatch(f"B has shape {tuple(d_B.shape)}, X has shape {tuple(d_X.shape)}, n={self.n}")
         ld = 2 * n if self.is_complex else n     # leading dimension in doubles
         with C.caller_stream(self._h, d_B):
+            if op != C.SMLU_OP_N:
+                return _check(C.lib().smlu_solve_trans_multi_device(
+                    self._h, op, nrhs, ctypes.c_void_p(d_B.data_ptr()), ld, ctypes.c_void_p(d_X.data_ptr()), ld),
+                    self._h)
             return _check(C.lib().smlu_solve_multi_device(self._h, nrhs, ctypes.c_void_p(d_B.data_ptr()), ld,
                                                           ctypes.c_void_p(d_X.data_ptr()), ld), self._h)
 
@@ -335,8 +357,11 @@ def lu_(F: ParallelSparseLU, A):
     return None
 
 
-def ldiv_(x, F: ParallelSparseLU, b):
-    """ldiv!(x, F, b) — src/SharedMemSparseLU.jl:286-342.  ``x is b`` is allowed."""
+def ldiv_(x, F: ParallelSparseLU, b, trans="N"):
+    """ldiv!(x, F, b) — src/SharedMemSparseLU.jl:286-342.  ``x is b`` is allowed.
+    trans="T" solves ``A.T x = b`` and trans="C" ``A.conj().T x = b`` from the same factors
+    (Julia's ``ldiv!(x, transpose(F), b)`` / ``ldiv!(x, F', b)``; smlu_solve_trans*)."""
+    op = _op(trans)
     if F.m != F.n:
         raise DimensionMismatch(f"`F` is not square: F.m={F.m}, F.n={F.n}")
     if len(x) != F.n:
@@ -356,14 +381,20 @@ def ldiv_(x, F: ParallelSparseLU, b):
         xx = x if (isinstance(x, np.ndarray) and x.dtype == dt and x.flags.f_contiguous) \
             else np.empty((F.n, nrhs), dtype=dt, order="F")
         ld = 2 * F.n if F.is_complex else F.n   # leading dimension in doubles
-        _check(C.lib().smlu_solve_multi(F._h, nrhs, C.ptr(bb), ld, C.ptr(xx), ld), F._h)
+        if op != C.SMLU_OP_N:
+            _check(C.lib().smlu_solve_trans_multi(F._h, op, nrhs, C.ptr(bb), ld, C.ptr(xx), ld), F._h)
+        else:
+            _check(C.lib().smlu_solve_multi(F._h, nrhs, C.ptr(bb), ld, C.ptr(xx), ld), F._h)
         if xx is not x:
             x[:, :] = xx
         return x
     bb = np.ascontiguousarray(b, dtype=F._dt)
     xx = x if (isinstance(x, np.ndarray) and x.dtype == F._dt and x.flags.c_contiguous) \
         else np.empty(F.n, dtype=F._dt)
-    _check(C.lib().smlu_solve(F._h, C.ptr(bb), C.ptr(xx)), F._h)
+    if op != C.SMLU_OP_N:
+        _check(C.lib().smlu_solve_trans(F._h, op, C.ptr(bb), C.ptr(xx)), F._h)
+    else:
+        _check(C.lib().smlu_solve(F._h, C.ptr(bb), C.ptr(xx)), F._h)
     if xx is not x:
         x[:] = xx
     return x

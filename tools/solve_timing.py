@@ -3,6 +3,14 @@ of 8 / 16 (smlu_solve_multi_device), median of several device-resident runs.  Ru
 `rocprofv3 --kernel-trace --stats` to split the time over the solve kernels.
 
     python tools/solve_timing.py [--side 128] [--reps 5]
+
+--trans: the transposed solve (smlu_solve_trans_device, A^T x = b) against its yardstick, the
+forward solve of a handle created under SMLU_SOLVE_STEPS=1 (the structurally identical per-block
+launch sequences), both on one handle in one process: warm-up, then alternating blocks of --reps
+solves each, median over all of them; host clock around a solve that ends in a device
+synchronise, clocks as the device runs them (no pinning).
+
+    python tools/solve_timing.py --trans [--side 128] [--reps 5]
 """
 import argparse
 import os
@@ -18,7 +26,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=128)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--trans", action="store_true")
     args = ap.parse_args()
+    if args.trans:
+        os.environ["SMLU_SOLVE_STEPS"] = "1"   # read when the handle's schedule is built
     import torch
     import smlu
     from smlu import matrices as mats
@@ -42,6 +53,32 @@ def main():
 
     b = torch.from_numpy(rng.random(n)).to(dev)
     x = torch.empty_like(b)
+    if args.trans:
+        assert F.stat("solve_sweeps") == 0
+        xt = torch.empty_like(b)
+        fwd = lambda: F.solve_device(x, b)
+        trn = lambda: F.solve_device(xt, b, trans="T")
+        ts = {"fwd": [], "trans": []}
+        for fn in (fwd, trn):   # warm-up: code objects, the captured graphs
+            for _ in range(2):
+                fn()
+        torch.cuda.synchronize()
+        for _ in range(3):      # alternating blocks
+            for key, fn in (("fwd", fwd), ("trans", trn)):
+                for _ in range(args.reps):
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    ts[key].append((time.perf_counter() - t0) * 1e3)
+        for key, v in ts.items():
+            out[f"ms_{key}"] = float(np.median(v))
+            out[f"ms_{key}_min_max"] = (float(min(v)), float(max(v)))
+        out["ratio_trans_fwd"] = out["ms_trans"] / out["ms_fwd"]
+        bh, xh = b.cpu().numpy(), xt.cpu().numpy()
+        out["resid_trans"] = float(np.abs(A.T @ xh - bh).max() / np.abs(bh).max())
+        out["resid_fwd"] = float(np.abs(A @ x.cpu().numpy() - bh).max() / np.abs(bh).max())
+        print(out, flush=True)
+        return
     out["ms_1"] = timed(lambda: F.solve_device(x, b))
     for k in (2, 4, 8, 16, 32):
         B = torch.from_numpy(rng.random((k, n))).to(dev)
