@@ -391,6 +391,12 @@ int smlu_plan_schedule_digest(const smlu_plan* plan, int32_t nparts, int32_t ran
  *                      GEMM-form TRSM onto the 128 tile when SMLU_T128MIN allows it)
  *   SMLU_FULLPIV_NS=k  largest front with full-candidate pivoting (tests; default: 512, or 0
  *                      for diagonally dominant values)
+ *   SMLU_F22_GATHER_NU=u  blocked fronts with at least u update rows (default 512) have their F22
+ *                      assembled inside the Schur GEMM's C prologue instead of by the assembly
+ *                      kernel (one GPU, real values, 128 MFMA tile only; bitwise the same factors);
+ *                      0 or negative: off.  smlu_stat: f22_gather_fronts, f22_gather_entries,
+ *                      launches_mfma128_gather
+ *   SMLU_F22_GATHER_CH=c  ... only fronts with at most c contributing children (default 8)
  *   SMLU_SWEEP_SPIN=s  polls before a sync-free solve wait gives up and the solve is re-run on the
  *                      per-block schedule (default 2^22; 0 = at once, tests)
  *   SMLU_SOLVE_STEPS=1 per-block solve launches instead of the sync-free sweeps

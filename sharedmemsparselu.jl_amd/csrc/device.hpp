@@ -40,6 +40,22 @@ struct GemmTask {
   int64_t tile0;
 };
 
+// F22 assembled in the Schur GEMM's C prologue (tile code 143): instead of loading C, a tile sums
+// the children's F22 entries in child order.  One F22Gather per task of such a launch (cnt = -1:
+// the plain C load), its children at F22Child[beg, beg + cnt).  inv (nu(parent) ints at
+// invmaps + inv) maps a parent F22 index to the child's F22 index, -1 where the child has none;
+// the child touches parent F22 indices [lo, hi] only.
+struct F22Gather {
+  int32_t beg, cnt;
+};
+struct F22Child {
+  int64_t foff;    // the child's F22 in the scratch arena (ld nu)
+  int64_t inv;
+  int32_t nu;
+  int32_t lo, hi;
+  int32_t pad;
+};
+
 // Fused U rows of an outer block (k_urows): one kUrowsCols-column block of the columns right of
 // the block; rows [ob0, ob1) of the block solved sub-panel by sub-panel (tinv slots slot0 + u).
 constexpr int kUrowsCols = 32;
@@ -82,6 +98,9 @@ struct SegDesc {
   int64_t n4;
 };
 
+// tj carries kXColNoF22 for a non-pivot column of a front whose F22 the Schur GEMM gathers
+// itself (F22Child below): the assembly then stops at row ns of that column.
+constexpr int32_t kXColNoF22 = 1 << 30;
 struct XCol {
   int32_t p, tj;
   int64_t off;

@@ -30,6 +30,9 @@ static hipError_t run_launch(smlu_handle* h, const Launch& L, double diag_tol, d
     case K_GEMMU:
     case K_GEMMO:
     case K_GEMM22:
+      if (L.aux == 143)   // some of its fronts' F22 is assembled in the tile's C prologue
+        return launch_gemm_gather(st, L.nwg, h->gtasks.p + L.off, (int)L.cnt, h->f22tasks.p + L.off2, h->f22ch.p,
+                                  h->f22inv.p, h->scratch.p);
       return launch_gemm(st, L.nwg, h->gtasks.p + L.off, (int)L.cnt, (int)L.aux, 0);
     case K_TRSML:
       return launch_gemm_g(st, L.nwg, h->gtasks.p + L.off, (int)L.cnt, (int)L.aux, 0, h->info.p,

@@ -48,6 +48,8 @@ hipError_t launch_trsm_u(hipStream_t, int64_t, const FrontTile*, int, int, int, 
                          double*, const int32_t*, int64_t);
 hipError_t launch_gemm(hipStream_t, int64_t, const GemmTask*, int, int, int64_t);
 hipError_t launch_gemm_g(hipStream_t, int64_t, const GemmTask*, int, int, int64_t, int32_t*, double*, double);
+hipError_t launch_gemm_gather(hipStream_t, int64_t, const GemmTask*, int, const F22Gather*, const F22Child*,
+                              const int32_t*, const double*);
 hipError_t launch_tri_inv(hipStream_t, int, int, const int32_t*, const SNode*, double*, double*, double*);
 hipError_t launch_urows(hipStream_t, int, const URowTask*, const SNode*, double*, const double*);
 hipError_t launch_fwd_tiny(hipStream_t, int, const int32_t*, const SNode*, const int32_t*, const int32_t*,
@@ -210,6 +212,9 @@ struct smlu_handle {
   DBuf<unsigned long long> stick; // ... one monotone ticket counter per sweep launch
   DBuf<double> sxh;               // ... hand-off slots: 64 x kMultiRhs doubles per flag
   DBuf<GemmTask> gtasks;
+  DBuf<F22Gather> f22tasks;   // F22 gathered by the Schur GEMM: per task, children, inverse row maps
+  DBuf<F22Child> f22ch;
+  DBuf<int32_t> f22inv;
   DBuf<SwapTask> stasks;
   DBuf<URowTask> urtasks;     // fused U-row tasks (k_urows)
   DBuf<XCol> xcols;
@@ -307,6 +312,9 @@ struct smlu_handle {
     stick.free();
     sxh.free();
     gtasks.free();
+    f22tasks.free();
+    f22ch.free();
+    f22inv.free();
     stasks.free();
     urtasks.free();
     xcols.free();

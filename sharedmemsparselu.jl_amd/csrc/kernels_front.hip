@@ -70,6 +70,8 @@ __global__ void k_factor_reset(int64_t nnodes, int32_t* __restrict__ info, doubl
 // Lane q < 64 keeps the running position of contribution q in its child column (row maps are
 // ascending, chunks are visited in ascending row order); contributions beyond the 64th find
 // their start by binary search.
+// A column flagged kXColNoF22 (a non-pivot column of a front whose F22 the Schur GEMM gathers in
+// its C prologue, kernels_gemm.hip) ends at row ns: its F22 part is neither built nor written here.
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_assemble(int64_t ntasks, const XCol* __restrict__ cols,
                                                   const XContrib* __restrict__ contrib,
@@ -88,8 +90,9 @@ __global__ __launch_bounds__(256) void k_assemble(int64_t ntasks, const XCol* __
   const XCol t = cols[w];
   const SNode p = sn[t.p];
   FrontPtrs P = front_ptrs(p, store, scratch);
-  const int64_t len = P.M;
-  const int64_t tj = t.tj;
+  // a flagged column's F22 rows are left to the Schur GEMM, which gathers them itself
+  const int64_t len = (t.tj & kXColNoF22) ? P.ns : P.M;
+  const int64_t tj = t.tj & ~kXColNoF22;
   // destination of local row r of this column
   gdbl* colL = tj < P.ns ? P.L + tj * P.M : nullptr;
   gdbl* colU = tj < P.ns ? nullptr : P.U + (tj - P.ns) * P.ns;

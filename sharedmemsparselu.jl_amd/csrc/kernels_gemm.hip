@@ -364,13 +364,58 @@ __global__ __launch_bounds__(256) void k_gemm_k64(const GemmTask* __restrict__ t
 #define HBM_ 128
 #define HBK_ 16
 #define HLDB_ (HBM_ + 2)
+// c ? x : +0.0 as a bit mask (keeps the compiler from sinking the load into a branch)
+__device__ __forceinline__ double sel0(bool c, double x) {
+  return __longlong_as_double(__double_as_longlong(x) & (c ? -1LL : 0LL));
+}
+// F22 gathered in the C prologue (tile code 143, device.hpp: F22Gather / F22Child): the tile starts
+// from the sum of the children's F22 entries -- what the assembly would have written to C -- formed
+// per entry as ((+0.0 + c1) + c2) + ... in child order.  A child without the entry adds +0.0, which
+// leaves the running sum's bits as they are (it starts at +0.0 and so is never -0.0).
+struct GatherArgs {
+  const F22Gather* tg;   // per task of the launch
+  const F22Child* ch;
+  const int32_t* inv;
+  const double* scratch;
+};
+struct F22Tile {         // one task's children (cnt < 0: plain C load)
+  const F22Child* ch;
+  const int32_t* inv;
+  const double* scratch;
+  int cnt;
+};
+// entry (ri, cj) of a child's F22 (ld nuc); +0.0 where either index is -1.  The load itself is
+// unconditional and in bounds (entry 0), the select a bit mask: no branch around a load.  Uniform
+// base + 32-bit byte offset per lane (the builder gathers only from children with 8 nu^2 < 2^32),
+// so an address costs one VGPR.
+__device__ __forceinline__ double f22_child_val(const char* src, int nuc, int ri, int cj) {
+  const bool ok = (ri | cj) >= 0;
+  const uint32_t off = ok ? ((uint32_t)cj * (uint32_t)nuc + (uint32_t)ri) * 8u : 0u;
+  return sel0(ok, *(const gdbl*)(src + off));
+}
+// The 16 entries rows ri[0..3] x columns cj[0..3] of one child added into acc[i][j][r], as one
+// group of loads: the scheduling fence keeps the next group's loads (and their 48 registers)
+// behind this group's additions, so the prologue stays inside the tile's register budget.
+__device__ __forceinline__ void f22_child_add(v4d (&acc)[4][4], int j, const char* src, int nuc, const int (&ri)[4],
+                                              const int (&cj)[4]) {
+  double v[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i][r] = f22_child_val(src, nuc, ri[i], cj[r]);
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i][j][r] += v[i][r];
+  __builtin_amdgcn_sched_barrier(0);
+}
 // Guard-free operand and C traffic on interior tiles (m, n in range), K guards only in the
 // last, partial slice (FULL = false: every access guarded).  +1-4 % over the guarded form
 // (k = 384 trailing shapes 48.4 -> 50.1 TFLOP/s, tools/gemm_bench).
-template <bool TRSM, bool FULL>
+template <bool TRSM, bool FULL, bool GATHER = false>
 __device__ __forceinline__ void gemm128_mfma_body(const GemmTask& t, int m0, int n0,
                                                 double (&As)[2][HBK_][HBM_], double (&Bs)[2][HBK_][HLDB_],
-                                                const GrowthArgs& ga) {
+                                                const GrowthArgs& ga, const F22Tile& fg = F22Tile{}) {
   const gdbl* gA = gbl(t.A);
   const gdbl* gB = gbl(t.B);
   gdbl* gC = gbl(t.C);
@@ -378,16 +423,50 @@ __device__ __forceinline__ void gemm128_mfma_body(const GemmTask& t, int m0, int
   const int wr = (wv & 1) * 64, wc = (wv >> 1) * 64;
   const int li = lane & 15, lk = lane >> 4;
   v4d acc[4][4];
+  if (GATHER && fg.cnt >= 0) {
+    // one child at a time: its row and column indices first (clamped reads, -1 outside the
+    // task), then the masked value loads
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = m0 + wr + 16 * i + li;
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
+      for (int j = 0; j < 4; ++j) acc[i][j] = v4d{0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+    for (int d = 0; d < fg.cnt; ++d) {
+      const F22Child c = fg.ch[d];
+      if (c.hi < m0 + wr || c.lo >= m0 + wr + 64 || c.hi < n0 + wc || c.lo >= n0 + wc + 64) continue;
+      const int32_t* inv = fg.inv + c.inv;
+      const char* src = reinterpret_cast<const char*>(fg.scratch + c.foff);
+      int ri[4], cj[4][4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int col = n0 + wc + 16 * j + lk + 4 * r;
-        acc[i][j][r] = (FULL || (row < t.m && col < t.n)) ? gC[(int64_t)col * t.ldc + row] : 0.0;
+      for (int i = 0; i < 4; ++i) {
+        const int row = m0 + wr + 16 * i + li;
+        const int v = inv[min(row, t.m - 1)];
+        ri[i] = row < t.m ? v : -1;
       }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int col = n0 + wc + 16 * j + lk + 4 * r;
+          const int v = inv[min(col, t.n - 1)];
+          cj[j][r] = col < t.n ? v : -1;
+        }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) f22_child_add(acc, j, src, c.nu, ri, cj[j]);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = m0 + wr + 16 * i + li;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int col = n0 + wc + 16 * j + lk + 4 * r;
+          acc[i][j][r] = (FULL || (row < t.m && col < t.n)) ? gC[(int64_t)col * t.ldc + row] : 0.0;
+        }
+    }
   }
   const int ar = tid & 127, ak = tid >> 7;
   const int bk = tid & 15, bc = tid >> 4;
@@ -505,9 +584,9 @@ __device__ __forceinline__ void glds16(const void* src, void* lds_dst) {
 }
 
 
-template <bool TRSM, bool EB>
+template <bool TRSM, bool EB, bool GATHER = false>
 __device__ __forceinline__ void gemm128_mfma3_interior(const GemmTask& t, int m0, int n0, Mfma3Lds& S,
-                                                       const GrowthArgs& ga) {
+                                                       const GrowthArgs& ga, const F22Tile& fg = F22Tile{}) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = (wv & 1) * 64, wc = (wv >> 1) * 64;
@@ -546,16 +625,46 @@ __device__ __forceinline__ void gemm128_mfma3_interior(const GemmTask& t, int m0
     }
   };
   v4d acc[4][4];
+  if (GATHER && fg.cnt >= 0) {
+    // C gathered from the children: the lane's rows m0 + wr + 32 ip + 2 li (+1) and columns
+    // n0 + wc + 16 j + lk + 4 r.  One child at a time: its 4 row and 16 column indices first, then
+    // the masked value loads; a child that misses this wave's quadrant is skipped (uniform test).
 #pragma unroll
-  for (int ip = 0; ip < 2; ++ip)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
+      for (int j = 0; j < 4; ++j) acc[i][j] = v4d{0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+    for (int d = 0; d < fg.cnt; ++d) {
+      const F22Child c = fg.ch[d];
+      if (c.hi < m0 + wr || c.lo >= m0 + wr + 64 || c.hi < n0 + wc || c.lo >= n0 + wc + 64) continue;
+      const int32_t* inv = fg.inv + c.inv;
+      const char* src = reinterpret_cast<const char*>(fg.scratch + c.foff);
+      int ri[4], cj[4][4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const v2d c = ldu2(cbase(ip, j, r), c_lo);
-        acc[2 * ip][j][r] = c.x;
-        acc[2 * ip + 1][j][r] = c.y;
+      for (int ip = 0; ip < 2; ++ip) {
+        ri[2 * ip] = inv[m0 + wr + 32 * ip + 2 * li];
+        ri[2 * ip + 1] = inv[m0 + wr + 32 * ip + 2 * li + 1];
       }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) cj[j][r] = inv[n0 + wc + 16 * j + lk + 4 * r];
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) f22_child_add(acc, j, src, c.nu, ri, cj[j]);
+    }
+  } else {
+#pragma unroll
+    for (int ip = 0; ip < 2; ++ip)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const v2d c = ldu2(cbase(ip, j, r), c_lo);
+          acc[2 * ip][j][r] = c.x;
+          acc[2 * ip + 1][j][r] = c.y;
+        }
+  }
   // fragment addresses: A row pair wr + 32 ip + 2 li at k = 4 kq + lk; B column wc + 16 j + li at
   // k = 4 kq + lk, i.e. pair 2 kq + (lk >> 1), slot that ^ (li >> 1), element lk & 1
   const int a_off = (lk * HBM_ + wr + 2 * li);
@@ -665,24 +774,30 @@ struct ClockMark {
   }
 };
 #endif
-template <bool TRSM, bool EB = false>
+template <bool TRSM, bool EB = false, bool GATHER = false>
 __global__ __launch_bounds__(256, 2) void k_gemm128_mfma3(const GemmTask* __restrict__ tasks, int ntask,
-                                                          GrowthArgs ga) {
+                                                          GrowthArgs ga, GatherArgs gx) {
 #ifdef SMLU_CLOCK_PROBE
   const ClockMark mark;
 #endif
   __shared__ __attribute__((aligned(16))) double lds[sizeof(Mfma3Lds) / sizeof(double)];
   const int64_t b = xcd_window_remap(blockIdx.x, gridDim.x);
-  const GemmTask t = tasks[find_gemm_task(tasks, ntask, b)];
+  const int ti = find_gemm_task(tasks, ntask, b);
+  const GemmTask t = tasks[ti];
+  F22Tile fg{nullptr, nullptr, nullptr, -1};
+  if (GATHER) {
+    const F22Gather g = gx.tg[ti];
+    fg = F22Tile{gx.ch + g.beg, gx.inv, gx.scratch, g.cnt};
+  }
   int tm, tn;
   tile_rc<HBM_>(t, b - t.tile0, tm, tn);
   const int m0 = tm * HBM_, n0 = tn * HBM_;
   if (m0 + HBM_ <= t.m && n0 + HBM_ <= t.n) {
-    gemm128_mfma3_interior<TRSM, EB>(t, m0, n0, *reinterpret_cast<Mfma3Lds*>(lds), ga);
+    gemm128_mfma3_interior<TRSM, EB, GATHER>(t, m0, n0, *reinterpret_cast<Mfma3Lds*>(lds), ga, fg);
   } else {
     auto& As = *reinterpret_cast<double(*)[2][HBK_][HBM_]>(lds);
     auto& Bs = *reinterpret_cast<double(*)[2][HBK_][HLDB_]>(lds + 2 * HBK_ * HBM_);
-    gemm128_mfma_body<TRSM, false>(t, m0, n0, As, Bs, ga);
+    gemm128_mfma_body<TRSM, false, GATHER>(t, m0, n0, As, Bs, ga, fg);
   }
 #ifdef SMLU_CLOCK_PROBE
   mark.done(EB ? 0 : 1);
@@ -709,10 +824,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm128_mfma3(const GemmTask* __rest
 #define UR_NC 32    // columns per workgroup
 #define UR_RB 6     // 16-row blocks per wave (OB <= 384 = 4 waves x 6 x 16)
 #define UR_LD 36    // LDS row stride of -C_u [k][col] (doubles)
-// c ? x : +0.0 as a bit mask (keeps the compiler from sinking the load into a branch)
-__device__ __forceinline__ double sel0(bool c, double x) {
-  return __longlong_as_double(__double_as_longlong(x) & (c ? -1LL : 0LL));
-}
 __global__ __launch_bounds__(256, 2) void k_urows(const URowTask* __restrict__ tasks, const SNode* __restrict__ sn,
                                                   double* __restrict__ store, const double* __restrict__ tinv) {
   __shared__ double Bs[64 * UR_LD];
@@ -939,11 +1050,13 @@ hipError_t launch_gemm_g(hipStream_t st, int64_t ntiles, const GemmTask* tasks, 
                          int64_t maxwg, int32_t* info, double* growth, double piv_tol) {
   if (ntiles <= 0) return hipSuccess;
   const GrowthArgs ga{info, growth, piv_tol};
+  const GatherArgs gx{nullptr, nullptr, nullptr, nullptr};
   const bool trsm = info != nullptr;
-  if (tile == 135 && trsm) k_gemm128_mfma3<true, true><<<(unsigned)ntiles, 256, 0, st>>>(tasks, ntask, ga);
-  else if (tile == 135) k_gemm128_mfma3<false, true><<<(unsigned)ntiles, 256, 0, st>>>(tasks, ntask, ga);
-  else if (tile == 131 && trsm) k_gemm128_mfma3<true><<<(unsigned)ntiles, 256, 0, st>>>(tasks, ntask, ga);
-  else if (tile == 131) k_gemm128_mfma3<false><<<(unsigned)ntiles, 256, 0, st>>>(tasks, ntask, ga);
+  if (tile == 143) return hipErrorInvalidValue;   // the gathering F22 tile: launch_gemm_gather
+  if (tile == 135 && trsm) k_gemm128_mfma3<true, true><<<(unsigned)ntiles, 256, 0, st>>>(tasks, ntask, ga, gx);
+  else if (tile == 135) k_gemm128_mfma3<false, true><<<(unsigned)ntiles, 256, 0, st>>>(tasks, ntask, ga, gx);
+  else if (tile == 131 && trsm) k_gemm128_mfma3<true><<<(unsigned)ntiles, 256, 0, st>>>(tasks, ntask, ga, gx);
+  else if (tile == 131) k_gemm128_mfma3<false><<<(unsigned)ntiles, 256, 0, st>>>(tasks, ntask, ga, gx);
   else if (tile == 65 && trsm) k_gemm_k64<true><<<(unsigned)ntiles, 256, 0, st>>>(tasks, ntask, ga);
   else if (tile == 65) k_gemm_k64<false><<<(unsigned)ntiles, 256, 0, st>>>(tasks, ntask, ga);
   else if (tile == 66 && trsm) k_gemm64_mfma<true><<<(unsigned)ntiles, 256, 0, st>>>(tasks, ntask, ga);
@@ -955,6 +1068,16 @@ hipError_t launch_gemm_g(hipStream_t st, int64_t ntiles, const GemmTask* tasks, 
 hipError_t launch_gemm(hipStream_t st, int64_t ntiles, const GemmTask* tasks, int ntask, int tile,
                        int64_t maxwg) {
   return launch_gemm_g(st, ntiles, tasks, ntask, tile, maxwg, nullptr, nullptr, 1.0);
+}
+// an F22 launch of tile code 143: task i of the launch has its gather record at tg[i]
+hipError_t launch_gemm_gather(hipStream_t st, int64_t ntiles, const GemmTask* tasks, int ntask, const F22Gather* tg,
+                              const F22Child* ch, const int32_t* inv, const double* scratch) {
+  if (ntiles <= 0) return hipSuccess;
+  if (!tg || !scratch) return hipErrorInvalidValue;   // (ch, inv: empty when no gathered front has children)
+  const GrowthArgs ga{nullptr, nullptr, 1.0};
+  const GatherArgs gx{tg, ch, inv, scratch};
+  k_gemm128_mfma3<false, true, true><<<(unsigned)ntiles, 256, 0, st>>>(tasks, ntask, ga, gx);
+  return hipGetLastError();
 }
 hipError_t launch_urows(hipStream_t st, int cnt, const URowTask* tasks, const SNode* sn, double* store,
                         const double* tinv) {

@@ -24,7 +24,9 @@ struct Tune {
   int64_t t128_min = 512;     // SMLU_T128MIN: 128x128 MFMA tiles from this many output tiles per launch
   bool small_k = true;        // SMLU_SMALLK=0: no one-shot k <= 64 GEMM tile
   int64_t fullpiv_ns = -1;    // SMLU_FULLPIV_NS: largest ns with full-candidate pivoting (-1 = default rule)
-  int sweep_spin = 1 << 22;   // SMLU_SWEEP_SPIN: polls before a sync-free solve wait gives up (0: at once)
+  int64_t f22_gather_nu = 512;  // SMLU_F22_GATHER_NU: fronts with nu >= this have their F22 assembled by the Schur GEMM (<= 0: off)
+  int64_t f22_gather_ch = 8;    // SMLU_F22_GATHER_CH: ... if at most this many children contribute
+  int sweep_spin = 1 << 22;  // SMLU_SWEEP_SPIN: polls before a sync-free solve wait gives up (0: at once)
   bool solve_steps = false;   // SMLU_SOLVE_STEPS=1: per-block solve launches instead of the sweeps
   bool no_graph = false;      // SMLU_NO_GRAPH: eager launches, no captured graphs
   bool debug_sync = false;    // SMLU_DEBUG_SYNC: synchronise after every launch (error localisation)

@@ -92,6 +92,11 @@ static int upload_schedule(smlu_handle* h) {
     }
   }
   HIPCHK(h->gtasks.upload(gt.data(), gt.size(), st));
+  if (!S.g22.empty()) {
+    HIPCHK(h->f22tasks.upload(S.g22.data(), S.g22.size(), st));
+    HIPCHK(h->f22ch.upload(S.g22ch.data(), S.g22ch.size(), st));
+    HIPCHK(h->f22inv.upload(S.g22inv.data(), S.g22inv.size(), st));
+  }
   HIPCHK(h->stasks.upload(S.st_tasks.data(), S.st_tasks.size(), st));
   HIPCHK(h->urtasks.upload(S.ur_tasks.data(), S.ur_tasks.size(), st));
   HIPCHK(h->xcols.upload(S.xc.data(), S.xc.size(), st));
@@ -127,7 +132,7 @@ static int upload_schedule(smlu_handle* h) {
   HIPCHK(hipStreamSynchronize(st));
   // the device holds the work lists and tasks now: only the launch records stay on the host
   S.ilist = {}; S.xt = {}; S.ae = {}; S.xc = {}; S.ft = {}; S.gptr = {}; S.gent = {};
-  S.gt = {}; S.st_tasks = {}; S.ur_tasks = {};
+  S.gt = {}; S.st_tasks = {}; S.ur_tasks = {}; S.g22 = {}; S.g22ch = {}; S.g22inv = {};
   return SMLU_OK;
 }
 
@@ -153,7 +158,9 @@ void schedule_bytes(const Plan& P, const RankLayout& lay, const Schedule& S, int
            4.0 * (double)(P.s_rows.size() + P.relmap.size() + P.ch_list.size()) + 4.0 * n * 2 + 4.0 * (double)nnodes +
            8.0 * (16 + 5 * 512) + out[3];
   // upload_schedule: sn, ilist, xtasks, aents, ftiles, gptr, gent, ssync, stick, sxh, sstatus,
-  // tinv, gtasks, stasks, urtasks, xcols, swaps, vbuf, segdesc
+  // tinv, gtasks (+ the F22 gather records, if any), stasks, urtasks, xcols, swaps, vbuf, segdesc
+  out[0] += sizeof(F22Gather) * (double)S.g22.size() + sizeof(F22Child) * (double)S.g22ch.size() +
+            4.0 * S.g22inv.size();
   out[0] += sizeof(SNode) * (double)S.hsn.size() + 4.0 * S.ilist.size() + sizeof(XContrib) * (double)S.xt.size() +
             sizeof(AEnt) * (double)S.ae.size() + sizeof(FrontTile) * (double)S.ft.size() +
             4.0 * (S.gptr.size() + S.gent.size()) + 4.0 * S.ssync_n + 8.0 * S.ntick +
@@ -245,6 +252,9 @@ static void release_schedule(smlu_handle* h) {
   h->stick.free();
   h->sxh.free();
   h->gtasks.free();
+  h->f22tasks.free();
+  h->f22ch.free();
+  h->f22inv.free();
   h->stasks.free();
   h->urtasks.free();
   h->xcols.free();

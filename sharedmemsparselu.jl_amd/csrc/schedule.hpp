@@ -104,6 +104,7 @@ struct GemmRec {
   int32_t tiles_m = 0;
   int32_t gsid = -1;
   int64_t tile0 = 0;
+  int32_t front = -1;   // F22 update of this front (builder only: neither hashed nor uploaded)
 };
 
 struct ScheduleInput {
@@ -141,6 +142,13 @@ struct Schedule {
   std::vector<GemmRec> gt;
   std::vector<SwapTask> st_tasks;
   std::vector<URowTask> ur_tasks;
+  // F22 gathered by the Schur GEMM (tile code 143): per task of such a launch (Launch.off2), the
+  // contributing children and their inverse row maps; all empty when no front qualifies
+  std::vector<F22Gather> g22;
+  std::vector<F22Child> g22ch;
+  std::vector<int32_t> g22inv;
+  int64_t f22_gather_fronts = 0;
+  double f22_gather_entries = 0;   // sum of nu^2 over those fronts
   // statistics
   double gemm_flops = 0, gemm22_flops = 0;
   double gemm_bytes = 0;      // algorithmic bytes of the GEMM launches: A, B read, C read + written

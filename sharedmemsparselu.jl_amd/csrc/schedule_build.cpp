@@ -44,6 +44,9 @@ int64_t tri_wg(bool upper, int64_t M, int64_t ns, int64_t jb) {
 // long-k shapes) take 135, the same tile with the next slice's barrier between its last two
 // k-quads (+3 % at k >= 2048, neutral at the k = 384 trailing shapes: tools/gemm_bench)
 constexpr int kMfmaTile = 131;
+// ... and 143 when some task of the F22 launch gathers its C from the children's F22 blocks
+// instead of loading what the assembly wrote (choose_f22_gather)
+constexpr int kMfmaGatherTile = 143;
 // look-ahead (depth 1) of the shared fronts: the owner of pivot block b+1 applies block b to block
 // b+1 first, factors and broadcasts b+1, and only then applies b to its other blocks (`pending`).
 // Off: the broadcast is a rendezvous (receivers post it after their own trailing updates), so the
@@ -75,6 +78,7 @@ struct Builder {
   std::vector<int64_t> bidx;
   std::vector<int32_t> col_cnt, col_pos;           // front_columns' counters
   std::vector<std::vector<Launch>> bwd_levels;     // backward launches per level, emitted root first
+  std::vector<char> f22g;                          // front -> its F22 is gathered by the Schur GEMM
 
   Builder(const ScheduleInput& i, Schedule& s)
       : in(i), P(*i.plan), Y(*i.lay), S(s), rank(i.rank), nranks(i.nranks) {}
@@ -158,6 +162,7 @@ struct Builder {
     if (step < 0)   // F22: longest k first, so the launch's last tiles are short ones
       std::stable_sort(cand.begin(), cand.end(), [](const GemmRec& a, const GemmRec& b) { return a.k > b.k; });
     Launch L = launch(step < 0 ? K_GEMM22 : kind, step, S.gt.size());
+    if (step < 0 && !f22_gather(cand, tile, L)) return;
     L.aux = tile;
     int64_t tiles = 0;
     const int ts = tile >= 128 ? 128 : 64;
@@ -178,6 +183,109 @@ struct Builder {
     ++S.gemm_launches;
     if (tile >= 128) ++S.gemm128_launches;
     if (step < 0) S.gemm22_flops += fl;
+  }
+
+  // ---- F22 assembled in the Schur GEMM's C prologue ---------------------------------------
+  // A blocked front's F22 holds no A entry (an entry belongs to the front of its pivot row or
+  // column), so what the assembly writes there is the sum of the children's F22 entries in child
+  // order -- written to HBM only for the level's F22 launch to read it back as C.  For the large
+  // fronts with few children the tile forms that sum itself (same order, same bits) and the
+  // assembly stops at row ns of their non-pivot columns.  One GPU, real values, and only where the
+  // level's F22 launch takes the 128 MFMA tile (the test below is add_gemm_launch's).
+  void choose_f22_gather(int l) {
+    if (nranks > 1 || in.cpair || !in.use_mfma || in.tn.f22_gather_nu <= 0) return;
+    int64_t t128 = 0;
+    for (int64_t k = LP[l]; k < LP[l + 1]; ++k) {
+      const SNode& r = S.hsn[LS[k]];
+      if (r.mode != 0 && r.nu > 0 && r.ns > 0) t128 += (int64_t)((r.nu + 127) / 128) * ((r.nu + 127) / 128);
+    }
+    if (t128 < S.t128_min) return;
+    for (int64_t k = LP[l]; k < LP[l + 1]; ++k) {
+      const int64_t s = LS[k];
+      const SNode& r = S.hsn[s];
+      if (r.mode == 0 || r.ns <= 0 || r.nu < in.tn.f22_gather_nu) continue;
+      int64_t nch = 0, numax = 0;
+      for (int64_t e = P.ch_ptr[s]; e < P.ch_ptr[s + 1]; ++e) {
+        nch += P.nu(P.ch_list[e]) > 0;
+        numax = std::max(numax, P.nu(P.ch_list[e]));
+      }
+      // (the tile addresses a child's F22 by 32-bit byte offsets: 8 nu^2 < 2^32)
+      if (nch <= in.tn.f22_gather_ch && numax <= 23170) f22g[s] = 1;
+    }
+  }
+  // The gather records of an F22 launch holding such fronts: per task the contributing children
+  // with their inverse row maps (parent F22 index -> child F22 index; one map serves rows and
+  // columns as the child's relmap does).  Checks that every map inverts its relmap and that the
+  // launch writes no F22 range a tile of it reads.  false: failed (err set).
+  bool f22_gather(const std::vector<GemmRec>& cand, int& tile, Launch& L) {
+    bool any = false;
+    for (const GemmRec& g : cand) any = any || (g.front >= 0 && f22g[g.front]);
+    if (!any) return true;
+    if (tile != 135) {
+      fail(kSchedErrState, "internal: F22 gather chosen for a launch off the 128 MFMA tile");
+      return false;
+    }
+    tile = kMfmaGatherTile;
+    L.off2 = (int64_t)S.g22.size();
+    std::vector<std::pair<int64_t, int64_t>> wr, rd;
+    for (const GemmRec& g : cand) {
+      wr.push_back({g.C.off, g.C.off + (int64_t)g.ldc * (g.n - 1) + g.m});
+      if (g.front < 0 || !f22g[g.front]) {
+        S.g22.push_back(F22Gather{0, -1});
+        continue;
+      }
+      const int64_t s = g.front, ns = P.ns(s), nu = P.nu(s);
+      F22Gather G{(int32_t)S.g22ch.size(), 0};
+      for (int64_t e = P.ch_ptr[s]; e < P.ch_ptr[s + 1]; ++e) {
+        const int64_t c = P.ch_list[e], nuc = P.nu(c);
+        if (nuc <= 0) continue;
+        const int32_t* rm = P.relmap.data() + S.hsn[c].rowptr;
+        const int64_t inv0 = (int64_t)S.g22inv.size();
+        S.g22inv.resize(inv0 + nu, -1);
+        int32_t* inv = S.g22inv.data() + inv0;
+        int64_t lo = nu, hi = -1, want = 0, have = 0;
+        for (int64_t jc = 0; jc < nuc; ++jc) {
+          const int64_t i = (int64_t)rm[jc] - ns;
+          if (i < 0) continue;
+          if (i >= nu) {
+            fail(kSchedErrState, "internal: a child's row map leaves its parent front");
+            return false;
+          }
+          inv[i] = (int32_t)jc;
+          lo = std::min(lo, i);
+          hi = std::max(hi, i);
+          ++want;
+        }
+        for (int64_t i = 0; i < nu; ++i) have += inv[i] >= 0;
+        bool ok = have == want;
+        for (int64_t jc = 0; jc < nuc && ok; ++jc)
+          if (rm[jc] >= ns) ok = inv[rm[jc] - ns] == jc;
+        if (!ok) {
+          fail(kSchedErrState, "internal: an F22 gather map does not invert its row map");
+          return false;
+        }
+        if (want == 0) {   // the child lands in the pivot rows and columns only
+          S.g22inv.resize(inv0);
+          continue;
+        }
+        S.g22ch.push_back(F22Child{S.hsn[c].Foff, inv0, (int32_t)nuc, (int32_t)lo, (int32_t)hi, 0});
+        rd.push_back({S.hsn[c].Foff, S.hsn[c].Foff + nuc * nuc});
+        ++G.cnt;
+      }
+      S.g22.push_back(G);
+      ++S.f22_gather_fronts;
+      S.f22_gather_entries += (double)nu * (double)nu;
+    }
+    std::sort(wr.begin(), wr.end());
+    for (size_t i = 1; i < wr.size(); ++i) wr[i].second = std::max(wr[i].second, wr[i - 1].second);   // running end
+    for (const auto& r : rd) {   // the written ranges that start below r's end must all end at or below its start
+      auto it = std::upper_bound(wr.begin(), wr.end(), std::make_pair(r.second, (int64_t)-1));
+      if (it != wr.begin() && std::prev(it)->second > r.first) {
+        fail(kSchedErrState, "internal: an F22 launch writes a child's F22 block it gathers from");
+        return false;
+      }
+    }
+    return true;
   }
 
   // ---- node records and block nodes -------------------------------------------------------
@@ -397,7 +505,9 @@ struct Builder {
           S.ae.push_back(AEnt{fr_ent[ea], P.A_li[fr_ent[ea]]});
           ++ea;
         }
-        S.xc.push_back(XCol{nodes[ri], (int32_t)tj, base + cnt[tj], cnt[tj + 1] - cnt[tj],
+        // a gathered front's non-pivot column stops at row ns (the lists stay whole)
+        const int32_t tjf = (int32_t)tj | (f22g[s] && tj >= P.ns(s) ? kXColNoF22 : 0);
+        S.xc.push_back(XCol{nodes[ri], tjf, base + cnt[tj], cnt[tj + 1] - cnt[tj],
                             (int32_t)((int64_t)S.ae.size() - a0), a0});
       }
   }
@@ -517,8 +627,10 @@ struct Builder {
     double fl = 0;
     for (auto s : big) {
       const SNode& r = S.hsn[s];
+      const size_t had = cand.size();
       update(cand, fl, kStore + r.Loff + r.ns, kStore + r.Uoff, kScratch + r.Foff, r.nu, r.nu, r.ns,
              (int64_t)r.ns + r.nu, r.ns, r.nu);
+      if (cand.size() > had) cand.back().front = (int32_t)s;
     }
     add_gemm_launch(cand, fl, -1);
   }
@@ -1335,7 +1447,9 @@ struct Builder {
     nodes();
     group_entries();
     levels();
+    f22g.assign(P.nsup, 0);
     for (int l = 0; l < P.nlevels && err.empty(); ++l) {
+      choose_f22_gather(l);
       assembly(l, f22_exchange(l));
       small_fronts(l);
       if (err.empty()) blocked_fronts(l);

@@ -256,8 +256,9 @@ double smlu_stat(const smlu_handle* h, const char* key) {
     for (const Launch& L : h->sch.fac) {
       const bool gemm = L.kind == K_GEMM || L.kind == K_GEMMU || L.kind == K_GEMMO || L.kind == K_GEMM22;
       const bool trsm = L.kind == K_TRSML;
-      const bool mfma = L.aux == 131 || L.aux == 135;
+      const bool mfma = L.aux == 131 || L.aux == 135 || L.aux == 143;
       if (v == "mfma128" && gemm && mfma) ++c;
+      else if (v == "mfma128_gather" && gemm && L.aux == 143) ++c;
       else if (v == "mfma128_trsm" && trsm && mfma) ++c;
       else if (v == "k64" && gemm && L.aux == 65) ++c;
       else if (v == "k64_trsm" && trsm && L.aux == 65) ++c;
@@ -288,6 +289,8 @@ double smlu_stat(const smlu_handle* h, const char* key) {
   if (k == "gemm22_flops") return h->sch.gemm22_flops;
   if (k == "gemm_launches") return (double)h->sch.gemm_launches;
   if (k == "gemm_bytes") return h->sch.gemm_bytes;
+  if (k == "f22_gather_fronts") return (double)h->sch.f22_gather_fronts;
+  if (k == "f22_gather_entries") return h->sch.f22_gather_entries;
   if (k == "gemm128_launches") return (double)h->sch.gemm128_launches;
   if (k == "vendor_calls") return 0.0;   // no vendor GEMM path (round 5)
   if (k.rfind("ms_", 0) == 0) {

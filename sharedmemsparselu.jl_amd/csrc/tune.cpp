@@ -14,6 +14,8 @@ Tune tune() {
     if (const char* e = std::getenv("SMLU_T128MIN")) v.t128_min = std::atoll(e);
     if (const char* e = std::getenv("SMLU_SMALLK")) v.small_k = std::atoi(e) != 0;
     if (const char* e = std::getenv("SMLU_FULLPIV_NS")) v.fullpiv_ns = std::atoll(e);
+    if (const char* e = std::getenv("SMLU_F22_GATHER_NU")) v.f22_gather_nu = std::atoll(e);
+    if (const char* e = std::getenv("SMLU_F22_GATHER_CH")) v.f22_gather_ch = std::atoll(e);
     if (const char* e = std::getenv("SMLU_SWEEP_SPIN")) v.sweep_spin = std::atoi(e);
     if (const char* e = std::getenv("SMLU_SOLVE_STEPS")) v.solve_steps = std::atoi(e) == 1;
     v.no_graph = std::getenv("SMLU_NO_GRAPH") != nullptr;

@@ -8,7 +8,7 @@ r.sort(key=lambda x: int(x["Start_Timestamp"]))
 
 
 def name(x):
-    return x["Kernel_Name"].split("(")[0].replace("smlu::", "").replace("void ", "")[:26]
+    return x["Kernel_Name"].split("(")[0].replace("smlu::", "").replace("void ", "")[:36]
 
 
 def summary(seg, title):
@@ -20,7 +20,7 @@ def summary(seg, title):
     span = (int(seg[-1]["End_Timestamp"]) - int(seg[0]["Start_Timestamp"])) / 1e6
     print(f"{title}: span {span:.1f} ms, busy {sum(tot.values()):.1f} ms, {len(seg)} launches")
     for k, v in sorted(tot.items(), key=lambda kv: -kv[1])[:14]:
-        print(f"  {k:28s} {v:8.2f} ms {cnt[k]:6d}  avg {1e3 * v / cnt[k]:8.1f} us")
+        print(f"  {k:38s} {v:8.2f} ms {cnt[k]:6d}  avg {1e3 * v / cnt[k]:8.1f} us")
 
 
 fac = [i for i, x in enumerate(r) if "k_rowscale" in x["Kernel_Name"]]

@@ -14,5 +14,7 @@ N = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 t0 = time.perf_counter()
 F = smlu.ParallelSparseLU(mats.poisson3d(N))
 print(f"N={N} factor+analysis {time.perf_counter() - t0:.1f}s gemm_launches={F.stat('gemm_launches'):.0f} "
-      f"gemm_bytes={F.stat('gemm_bytes'):.6g} gemm_flops={F.stat('gemm_flops'):.6g}", flush=True)
+      f"gemm_bytes={F.stat('gemm_bytes'):.6g} gemm_flops={F.stat('gemm_flops'):.6g} "
+      f"f22_gather_fronts={F.stat('f22_gather_fronts'):.0f} f22_gather_entries={F.stat('f22_gather_entries'):.6g} "
+      f"fronts_blocked={F.stat('fronts_mode1') + F.stat('fronts_mode2'):.0f}", flush=True)
 F.close()
