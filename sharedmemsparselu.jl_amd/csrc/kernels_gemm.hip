@@ -363,7 +363,6 @@ __global__ __launch_bounds__(256) void k_gemm_k64(const GemmTask* __restrict__ t
 // C[row = 16 bi + (l & 15)][col = 16 bj + (l >> 4) + 4 r], r = 0..3.
 #define HBM_ 128
 #define HBK_ 16
-#define HLDB_ (HBM_ + 2)
 // c ? x : +0.0 as a bit mask (keeps the compiler from sinking the load into a branch)
 __device__ __forceinline__ double sel0(bool c, double x) {
   return __longlong_as_double(__double_as_longlong(x) & (c ? -1LL : 0LL));
@@ -393,150 +392,23 @@ __device__ __forceinline__ double f22_child_val(const char* src, int nuc, int ri
   const uint32_t off = ok ? ((uint32_t)cj * (uint32_t)nuc + (uint32_t)ri) * 8u : 0u;
   return sel0(ok, *(const gdbl*)(src + off));
 }
-// The 16 entries rows ri[0..3] x columns cj[0..3] of one child added into acc[i][j][r], as one
+// The 4 NI entries rows ri[0..NI) x columns cj[0..3] of one child added into acc[i][j][r], as one
 // group of loads: the scheduling fence keeps the next group's loads (and their 48 registers)
 // behind this group's additions, so the prologue stays inside the tile's register budget.
-__device__ __forceinline__ void f22_child_add(v4d (&acc)[4][4], int j, const char* src, int nuc, const int (&ri)[4],
+template <int NI, int NJ>
+__device__ __forceinline__ void f22_child_add(v4d (&acc)[NI][NJ], int j, const char* src, int nuc, const int (&ri)[NI],
                                               const int (&cj)[4]) {
-  double v[4][4];
+  double v[NI][4];
 #pragma unroll
   for (int r = 0; r < 4; ++r)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) v[i][r] = f22_child_val(src, nuc, ri[i], cj[r]);
+    for (int i = 0; i < NI; ++i) v[i][r] = f22_child_val(src, nuc, ri[i], cj[r]);
 #pragma unroll
   for (int r = 0; r < 4; ++r)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i][j][r] += v[i][r];
+    for (int i = 0; i < NI; ++i) acc[i][j][r] += v[i][r];
   __builtin_amdgcn_sched_barrier(0);
 }
-// Guard-free operand and C traffic on interior tiles (m, n in range), K guards only in the
-// last, partial slice (FULL = false: every access guarded).  +1-4 % over the guarded form
-// (k = 384 trailing shapes 48.4 -> 50.1 TFLOP/s, tools/gemm_bench).
-template <bool TRSM, bool FULL, bool GATHER = false>
-__device__ __forceinline__ void gemm128_mfma_body(const GemmTask& t, int m0, int n0,
-                                                double (&As)[2][HBK_][HBM_], double (&Bs)[2][HBK_][HLDB_],
-                                                const GrowthArgs& ga, const F22Tile& fg = F22Tile{}) {
-  const gdbl* gA = gbl(t.A);
-  const gdbl* gB = gbl(t.B);
-  gdbl* gC = gbl(t.C);
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int wr = (wv & 1) * 64, wc = (wv >> 1) * 64;
-  const int li = lane & 15, lk = lane >> 4;
-  v4d acc[4][4];
-  if (GATHER && fg.cnt >= 0) {
-    // one child at a time: its row and column indices first (clamped reads, -1 outside the
-    // task), then the masked value loads
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = v4d{0.0, 0.0, 0.0, 0.0};
-#pragma unroll 1
-    for (int d = 0; d < fg.cnt; ++d) {
-      const F22Child c = fg.ch[d];
-      if (c.hi < m0 + wr || c.lo >= m0 + wr + 64 || c.hi < n0 + wc || c.lo >= n0 + wc + 64) continue;
-      const int32_t* inv = fg.inv + c.inv;
-      const char* src = reinterpret_cast<const char*>(fg.scratch + c.foff);
-      int ri[4], cj[4][4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = m0 + wr + 16 * i + li;
-        const int v = inv[min(row, t.m - 1)];
-        ri[i] = row < t.m ? v : -1;
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int col = n0 + wc + 16 * j + lk + 4 * r;
-          const int v = inv[min(col, t.n - 1)];
-          cj[j][r] = col < t.n ? v : -1;
-        }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) f22_child_add(acc, j, src, c.nu, ri, cj[j]);
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = m0 + wr + 16 * i + li;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int col = n0 + wc + 16 * j + lk + 4 * r;
-          acc[i][j][r] = (FULL || (row < t.m && col < t.n)) ? gC[(int64_t)col * t.ldc + row] : 0.0;
-        }
-    }
-  }
-  const int ar = tid & 127, ak = tid >> 7;
-  const int bk = tid & 15, bc = tid >> 4;
-  const int K = t.k;
-  const int arow = m0 + ar;
-  const bool arow_ok = FULL || arow < t.m;
-  const gdbl* Ap = gA + arow;
-  const gdbl* Bp = gB + (int64_t)(n0 + bc) * t.ldb + bk;
-  double ra[8], rb[8];
-  auto gload = [&](int k0, bool kguard) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const int kk = k0 + ak + 2 * r;
-      if (!kguard && FULL) ra[r] = Ap[(int64_t)kk * t.lda];
-      else ra[r] = (arow_ok && kk < K) ? Ap[(int64_t)kk * t.lda] : 0.0;
-      const int col = n0 + bc + 16 * r;
-      if (!kguard && FULL) rb[r] = Bp[(int64_t)16 * r * t.ldb + k0];
-      else rb[r] = ((FULL || col < t.n) && k0 + bk < K) ? Bp[(int64_t)16 * r * t.ldb + k0] : 0.0;
-    }
-  };
-  auto sstore = [&](int buf) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      As[buf][ak + 2 * r][ar] = ra[r];
-      Bs[buf][bk][bc + 16 * r] = -rb[r];
-    }
-  };
-  const int nk = (K + HBK_ - 1) / HBK_;
-  const int nfull = K / HBK_;   // slices with every k in range
-  gload(0, nfull == 0);
-  sstore(0);
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) gload((kt + 1) * HBK_, kt + 1 >= nfull);
-#pragma unroll
-    for (int kq = 0; kq < HBK_ / 4; ++kq) {
-      const int k = kq * 4 + lk;
-      double fa[4], fb[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fa[i] = As[cur][k][wr + 16 * i + li];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) fb[j] = Bs[cur][k][wc + 16 * j + li];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[j], fa[i], acc[i][j], 0, 0, 0);
-    }
-    if (kt + 1 < nk) sstore(cur ^ 1);
-    __syncthreads();
-  }
-  double gmax = 0.0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = m0 + wr + 16 * i + li;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int col = n0 + wc + 16 * j + lk + 4 * r;
-        if (FULL || (row < t.m && col < t.n)) {
-          gC[(int64_t)col * t.ldc + row] = acc[i][j][r];
-          if (TRSM) gmax = fmax(gmax, fabs(acc[i][j][r]));
-        }
-      }
-  }
-  if (TRSM && t.gsid >= 0) tile_growth(ga, t.gsid, gmax);
-}
-
 
 // Pair types and global accessors of the v3 tile.
 typedef double v2du __attribute__((ext_vector_type(2), aligned(8)));   // 8-byte aligned pairs (global)
@@ -570,7 +442,7 @@ __device__ __forceinline__ void stu2(char* ubase, uint32_t off, v2d v) {
 //    barrier);
 //  * a partial last slice (K % 16) is staged through registers with zero fill, into the same
 //    images (no guard in the compute loop).
-// Interior tiles only; edge tiles take gemm128_mfma_body<.., false> (same arithmetic).
+// Interior tiles only; edge tiles take gemm128_mfma3_edge (same arithmetic).
 // ------------------------------------------------------------------------------------
 struct Mfma3Lds {
   double A[2][HBK_][HBM_];   // [buf][k][row]
@@ -754,6 +626,232 @@ __device__ __forceinline__ void gemm128_mfma3_interior(const GemmTask& t, int m0
   if (TRSM && t.gsid >= 0) tile_growth(ga, t.gsid, gmax);
 }
 
+// ------------------------------------------------------------------------------------
+// Edge tiles of the v3 tile: lm = min(128, m - m0) live rows, ln = min(128, n - n0) live columns,
+// not both 128.  Same LDS images, fragment reads and per-element arithmetic as the interior (acc = C
+// or the gathered child sum, one MFMA multiply-add per k, ascending, B negated by the MFMA
+// modifier), so the results are bitwise those of every other tile.  What differs:
+//  * the four waves are laid over the live region (LAYOUT, chosen per workgroup from lm, ln):
+//      0  lm > 64, ln > 64   2 x 2 quadrants of 64 x 64 (the interior's layout)
+//      1  ln <= 64           four 32-row strips x 64 columns
+//      2  lm <= 64           64 rows x four 32-column strips
+//      3  both <= 64         2 x 2 of 32 x 32
+//    and inside a wave the MFMA blocks beyond the live extent are skipped by uniform branches
+//    around statically indexed accumulators (32-row granularity: an accumulator pair holds the
+//    even and odd rows of a 32-row block; 16-column granularity);
+//  * operand rows and columns outside the task are replaced by clamped (in-range) ones: a row of A
+//    beyond m or a column of B beyond n feeds only outputs that are never stored.  B always goes by
+//    LDS-DMA; A goes by LDS-DMA when every lane's 16-byte row pair lies inside the column (lm even
+//    or 128) and through registers (two clamped 8-byte loads per lane) when m is odd.  The partial
+//    last K slice is zero filled through registers as in the interior;
+//  * C is loaded from clamped addresses without guards (an accumulator entry outside the task
+//    holds some other entry's value and is never stored) and stored under one guard per row pair
+//    and column; the growth maximum is taken over stored entries only.
+// Every global access is inside the task's operands for every lane.
+// ------------------------------------------------------------------------------------
+template <bool TRSM, bool GATHER, int LAYOUT>
+__device__ __forceinline__ void gemm128_mfma3_edge(const GemmTask& t, int m0, int n0, int lm, int ln, Mfma3Lds& S,
+                                                   const GrowthArgs& ga, const F22Tile& fg) {
+  constexpr int NIP = (LAYOUT == 0 || LAYOUT == 2) ? 2 : 1;   // 32-row blocks (accumulator pairs) per wave
+  constexpr int NJ = (LAYOUT == 0 || LAYOUT == 1) ? 4 : 2;    // 16-column blocks per wave
+  constexpr int BQ = (LAYOUT == 0 || LAYOUT == 2) ? 4 : 2;    // B staging steps per wave (columns >= 64 unread when ln <= 64)
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wr = LAYOUT == 0 ? (wv & 1) * 64 : LAYOUT == 1 ? wv * 32 : LAYOUT == 2 ? 0 : (wv & 1) * 32;
+  const int wc = LAYOUT == 0 ? (wv >> 1) * 64 : LAYOUT == 1 ? 0 : LAYOUT == 2 ? wv * 32 : (wv >> 1) * 32;
+  const int li = lane & 15, lk = lane >> 4;
+  const int K = t.k;
+  const int64_t lda = t.lda, ldb = t.ldb;
+  const uint32_t ldc = (uint32_t)t.ldc;
+  // live blocks of this wave (uniform)
+  const int nipl = min(NIP, max(0, (lm - wr + 31) >> 5));
+  const int njl = min(NJ, max(0, (ln - wc + 15) >> 4));
+  const bool live = nipl > 0 && njl > 0;
+  // C: uniform tile origin + 32-bit byte offset per lane (tile-relative row rl, column cl; at most
+  // 8 (127 ldc + 127) bytes: fits for any front that fits in memory)
+  char* cb = reinterpret_cast<char*>(t.C) + ((int64_t)n0 * t.ldc + m0) * 8;
+  v4d acc[2 * NIP][NJ];
+  if (GATHER && fg.cnt >= 0) {
+    // as in the interior, with the row and column indices read at clamped positions (-1 outside
+    // the task) and the child test on this wave's live rows and columns
+#pragma unroll
+    for (int i = 0; i < 2 * NIP; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[i][j] = v4d{0.0, 0.0, 0.0, 0.0};
+    if (live) {
+#pragma unroll 1
+      for (int d = 0; d < fg.cnt; ++d) {
+        const F22Child c = fg.ch[d];
+        if (c.hi < m0 + wr || c.lo >= m0 + wr + 32 * nipl || c.hi < n0 + wc || c.lo >= n0 + wc + 16 * njl) continue;
+        const int32_t* inv = fg.inv + c.inv;
+        const char* src = reinterpret_cast<const char*>(fg.scratch + c.foff);
+        int ri[2 * NIP], cj[NJ][4];
+#pragma unroll
+        for (int i = 0; i < 2 * NIP; ++i) {
+          const int row = m0 + wr + 32 * (i >> 1) + 2 * li + (i & 1);
+          const int v = inv[min(row, t.m - 1)];
+          ri[i] = row < t.m ? v : -1;
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int col = n0 + wc + 16 * j + lk + 4 * r;
+            const int v = inv[min(col, t.n - 1)];
+            cj[j][r] = col < t.n ? v : -1;
+          }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          if (j < njl) f22_child_add(acc, j, src, c.nu, ri, cj[j]);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int ip = 0; ip < NIP; ++ip) {
+      const int rl = wr + 32 * ip + 2 * li;
+      const int rc = min(rl, lm - 2);   // pair start inside the column (lm >= 2)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const uint32_t cl = (uint32_t)min(wc + 16 * j + lk + 4 * r, ln - 1);
+          if (lm >= 2) {
+            const v2d c = ldu2(cb, (cl * ldc + (uint32_t)rc) * 8u);
+            acc[2 * ip][j][r] = rl > rc ? c.y : c.x;   // odd m: row m - 1 is the pair's second entry
+            acc[2 * ip + 1][j][r] = c.y;
+          } else {
+            acc[2 * ip][j][r] = acc[2 * ip + 1][j][r] = *(const gdbl*)(cb + cl * ldc * 8u);
+          }
+        }
+    }
+  }
+  // staging.  B by LDS-DMA: slot column 8 (wv + 4q) + (lane >> 3) from source column min(slot, ln - 1).
+  const int bpair = (lane & 7) ^ ((4 * wv + (lane >> 4)) & 7);
+  const char* bbase = reinterpret_cast<const char*>(t.B) + ((int64_t)n0 * ldb + 2 * bpair) * 8;
+  auto bsrc = [&](int q, int k0) {
+    return bbase + ((int64_t)min(8 * (wv + 4 * q) + (lane >> 3), ln - 1) * ldb + k0) * 8;
+  };
+  // A: k-row wv + 4q of the slice; by LDS-DMA the row pair min(2 lane, lm - 2), +1
+  const bool a_dma = lm == HBM_ || !(lm & 1);
+  const char* abase = reinterpret_cast<const char*>(t.A) + ((int64_t)wv * lda + m0) * 8;
+  const uint32_t a_pair = (uint32_t)max(min(2 * lane, lm - 2), 0) * 8u;
+  const uint32_t a_x = (uint32_t)min(2 * lane, lm - 1) * 8u, a_y = (uint32_t)min(2 * lane + 1, lm - 1) * 8u;
+  auto issue = [&](int k0, int buf) {   // one full slice (k0 + 16 <= K)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (a_dma) glds16(abase + ((int64_t)(k0 + 4 * q) * lda) * 8 + a_pair, &S.A[buf][wv + 4 * q][0]);
+      if (q < BQ) glds16(bsrc(q, k0), &S.B[buf][8 * (wv + 4 * q)][0]);
+    }
+  };
+  auto tail_b = [&](int k0, int buf) {   // partial slice: guarded register loads, zero fill
+#pragma unroll
+    for (int q = 0; q < BQ; ++q) {
+      const gdbl* bp = gbl(reinterpret_cast<const double*>(bsrc(q, k0)));
+      const int kb = k0 + 2 * bpair;
+      v2d b;
+      b.x = kb < K ? bp[0] : 0.0;
+      b.y = kb + 1 < K ? bp[1] : 0.0;
+      *reinterpret_cast<v2d*>(&S.B[buf][8 * (wv + 4 * q)][2 * lane]) = b;
+    }
+  };
+  v2d areg[4];
+  auto load_a = [&](int k0) {   // A through registers: clamped rows, zero beyond K
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const char* p = abase + ((int64_t)(k0 + 4 * q) * lda) * 8;
+      if (k0 + wv + 4 * q < K) areg[q] = v2d{*(const gdbl*)(p + a_x), *(const gdbl*)(p + a_y)};
+      else areg[q] = v2d{0.0, 0.0};
+    }
+  };
+  auto store_a = [&](int buf) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) *reinterpret_cast<v2d*>(&S.A[buf][wv + 4 * q][2 * lane]) = areg[q];
+  };
+  // fragments as in the interior, at this layout's wave origin
+  const int a_off = (lk * HBM_ + wr + 2 * li);
+  int b_off[4];
+#pragma unroll
+  for (int kq = 0; kq < 4; ++kq) b_off[kq] = (wc + li) * HBK_ + (((2 * kq + (lk >> 1)) ^ (li >> 1)) << 1) + (lk & 1);
+  auto frags = [&](int cur, int kq, v2d (&fa)[NIP], double (&fb)[NJ]) {
+    const double* As = &S.A[cur][0][0] + a_off + kq * 4 * HBM_;
+    const double* Bs = &S.B[cur][0][0] + b_off[kq];
+#pragma unroll
+    for (int ip = 0; ip < NIP; ++ip) fa[ip] = *reinterpret_cast<const v2d*>(As + 32 * ip);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) fb[j] = Bs[16 * HBK_ * j];
+  };
+  auto quad = [&](const v2d (&fa)[NIP], const double (&fb)[NJ]) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+      if (j < njl) {
+#pragma unroll
+        for (int ip = 0; ip < NIP; ++ip)
+          if (ip < nipl) {   // neg:[1,0,0]: C - B*A
+            acc[2 * ip][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[j], fa[ip].x, acc[2 * ip][j], 0, 0, 1);
+            acc[2 * ip + 1][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[j], fa[ip].y, acc[2 * ip + 1][j], 0, 0, 1);
+          }
+      }
+  };
+  auto slice = [&](int cur) {
+    v2d fa0[NIP], fa1[NIP];
+    double fb0[NJ], fb1[NJ];
+    frags(cur, 0, fa0, fb0);
+    frags(cur, 1, fa1, fb1);
+    quad(fa0, fb0);
+    frags(cur, 2, fa0, fb0);
+    quad(fa1, fb1);
+    frags(cur, 3, fa1, fb1);
+    quad(fa0, fb0);
+    quad(fa1, fb1);
+  };
+  const int nk = (K + HBK_ - 1) / HBK_;
+  const int nfull = K / HBK_;
+  if (nfull > 0) issue(0, 0);
+  else tail_b(0, 0);
+  if (!(a_dma && nfull > 0)) {
+    load_a(0);
+    store_a(0);
+  }
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int cur = kt & 1;
+    const bool next = kt + 1 < nk;
+    const bool next_full = kt + 1 < nfull;
+    const bool a_regs = next && !(a_dma && next_full);
+    if (next_full) issue((kt + 1) * HBK_, cur ^ 1);
+    if (next && !next_full) tail_b((kt + 1) * HBK_, cur ^ 1);
+    if (a_regs) load_a((kt + 1) * HBK_);   // in flight during this slice's MFMAs
+    if (live) slice(cur);
+    if (a_regs) store_a(cur ^ 1);
+    if (next) __syncthreads();
+  }
+  double gmax = 0.0;
+#pragma unroll
+  for (int ip = 0; ip < NIP; ++ip)
+    if (ip < nipl) {
+      const int rl = wr + 32 * ip + 2 * li;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        if (j < njl) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int cl = wc + 16 * j + lk + 4 * r;
+            const uint32_t off = ((uint32_t)cl * ldc + (uint32_t)rl) * 8u;
+            const double x = acc[2 * ip][j][r], y = acc[2 * ip + 1][j][r];
+            if (cl < ln && rl + 1 < lm) {
+              stu2(cb, off, v2d{x, y});
+              if (TRSM) gmax = fmax(gmax, fmax(fabs(x), fabs(y)));
+            } else if (cl < ln && rl < lm) {
+              *(gdbl*)(cb + off) = x;
+              if (TRSM) gmax = fmax(gmax, fabs(x));
+            }
+          }
+        }
+    }
+  if (TRSM && t.gsid >= 0) tile_growth(ga, t.gsid, gmax);
+}
+
 #ifdef SMLU_CLOCK_PROBE
 // Dev build only (tools/gemm_clock.py): the shader clock the 128 tile runs at, from the
 // workgroup's own counters -- sum of delta s_memtime (shader cycles) and of delta s_memrealtime
@@ -795,9 +893,13 @@ __global__ __launch_bounds__(256, 2) void k_gemm128_mfma3(const GemmTask* __rest
   if (m0 + HBM_ <= t.m && n0 + HBM_ <= t.n) {
     gemm128_mfma3_interior<TRSM, EB, GATHER>(t, m0, n0, *reinterpret_cast<Mfma3Lds*>(lds), ga, fg);
   } else {
-    auto& As = *reinterpret_cast<double(*)[2][HBK_][HBM_]>(lds);
-    auto& Bs = *reinterpret_cast<double(*)[2][HBK_][HLDB_]>(lds + 2 * HBK_ * HBM_);
-    gemm128_mfma_body<TRSM, false, GATHER>(t, m0, n0, As, Bs, ga, fg);
+    // edge tile: the wave layout follows the live extents (uniform per workgroup)
+    Mfma3Lds& S = *reinterpret_cast<Mfma3Lds*>(lds);
+    const int lm = min(HBM_, t.m - m0), ln = min(HBM_, t.n - n0);
+    if (lm > 64 && ln > 64) gemm128_mfma3_edge<TRSM, GATHER, 0>(t, m0, n0, lm, ln, S, ga, fg);
+    else if (lm > 64) gemm128_mfma3_edge<TRSM, GATHER, 1>(t, m0, n0, lm, ln, S, ga, fg);
+    else if (ln > 64) gemm128_mfma3_edge<TRSM, GATHER, 2>(t, m0, n0, lm, ln, S, ga, fg);
+    else gemm128_mfma3_edge<TRSM, GATHER, 3>(t, m0, n0, lm, ln, S, ga, fg);
   }
 #ifdef SMLU_CLOCK_PROBE
   mark.done(EB ? 0 : 1);

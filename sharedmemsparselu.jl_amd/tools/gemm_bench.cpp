@@ -16,6 +16,17 @@ int main(int argc, char** argv) {
   struct Shape { int m, n, k, lda = 0, ldb = 0, ldc = 0; } shapes[] = {{4096, 4096, 4096}, {8192, 8192, 1024}, {16384, 16384, 64}, {12000, 12000, 6000}, {1000, 1000, 300}, {300, 5000, 32}, {777, 1333, 129},
                                             {18000, 192, 64}, {192, 18000, 64}, {6000, 6000, 256}, {3000, 3000, 256}, {1500, 1500, 1000}, {18000, 256, 256}};
   std::vector<Shape> sv(std::begin(shapes), std::end(shapes));
+  // ragged shapes (the 128 tile's edge path): m = n = 128 j + r with a live extent r of 1, 40, 64, 65
+  // and 127 in the last tile row and column, at the k of the in-block, trailing and F22 updates;
+  // one edge tile column only (n = 128 + r); the in-block shapes whose last tile is 64 columns wide
+  for (int r : {1, 40, 64, 65, 127})
+    for (int k : {64, 384, 2048}) sv.push_back({3072 + r, 3072 + r, k});
+  for (int r : {1, 40, 64, 65, 127}) sv.push_back({18000, 128 + r, 384});
+  for (int r : {40, 64, 127}) sv.push_back({128 + r, 18000, 384});
+  sv.push_back({18000, 320, 64});
+  sv.push_back({18000, 192, 64});
+  sv.push_back({18000, 64, 64});
+  sv.push_back({3072, 3072, 384});   // no edge tile
   if (argc > 1) {   // shapes from the command line: m,n,k ...
     sv.clear();
     for (int a = 1; a < argc; ++a) {   // m,n,k or m,n,k,lda,ldb,ldc
@@ -23,8 +34,8 @@ int main(int argc, char** argv) {
       if (sscanf(argv[a], "%d,%d,%d,%d,%d,%d", &x.m, &x.n, &x.k, &x.lda, &x.ldb, &x.ldc) >= 3) sv.push_back(x);
     }
   }
-  // variants: tile codes of launch_gemm (GB_TILES="128,130"); the first one is the reference
-  std::vector<int> tiles_list = {64, 128, 130};
+  // variants: tile codes of launch_gemm (GB_TILES="131,135"); the first one is the reference
+  std::vector<int> tiles_list = {64, 131, 135};
   if (const char* e = std::getenv("GB_TILES")) {
     tiles_list.clear();
     for (const char* p = e; *p;) { tiles_list.push_back(std::atoi(p)); while (*p && *p != ',') ++p; if (*p) ++p; }
