@@ -435,11 +435,15 @@ __device__ __forceinline__ void stu2(char* ubase, uint32_t off, v2d v) {
 //    half-wave -- bank-conflict free;
 //  * B's sign flip is the MFMA's own neg modifier on the B fragment (exact: -b*a = b*(-a)), so no
 //    staging VALU work and no staging registers: the 32 VGPRs v2 spent on the in-flight slice
-//    hold a second fragment set instead, and the fragments of k-quad q+1 are read while the 16
-//    MFMAs of quad q run;
-//  * one barrier per slice, which also retires the slice's DMA (the next slice's DMA is issued
-//    at the top of the current slice, into the other buffer, whose readers passed the previous
-//    barrier);
+//    hold a second fragment set instead.  In the interior tile the fragments of k-quad q+1 are read
+//    behind the first MFMA of quad q and waited for behind its last (pinned by scheduling fences;
+//    tools/isa_kloop.py --check reads it back from the assembly); the edge tiles leave the
+//    placement to the compiler;
+//  * one barrier per slice, which also retires the slice's DMA.  The next slice's DMA goes into
+//    the other buffer, whose readers passed the previous barrier: in the interior tile behind the
+//    first MFMAs of quad 0, two loads at a time, with the barrier between quads 2 and 3 (every
+//    instantiation; the EB parameter no longer changes the interior loop); in the edge tiles at
+//    the top of the slice with the barrier at its end;
 //  * a partial last slice (K % 16) is staged through registers with zero fill, into the same
 //    images (no guard in the compute loop).
 // Interior tiles only; edge tiles take gemm128_mfma3_edge (same arithmetic).
@@ -455,6 +459,75 @@ __device__ __forceinline__ void glds16(const void* src, void* lds_dst) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (lds_void*)lds_dst, 16, 0, 0);
 }
 
+// A wave-uniform pointer pinned in scalar registers: base + (32-bit lane offset) then selects the
+// scalar-base form of the load, and the base arithmetic stays on the scalar ALU.
+__device__ __forceinline__ const char* uniform_ptr(const char* p) {
+  const uint64_t v = reinterpret_cast<uint64_t>(p);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
+}
+
+// The same LDS-DMA load in its scalar-base form, global_load_lds_dwordx4 voff, s[base]: source =
+// wave-uniform base + 32-bit lane offset, no vector ALU work per load.  (The compiler's selection
+// of this form needs the zero extension of the offset in the load's own basic block, which loop
+// hoisting defeats, hence the instruction by name.)  The compiler does not count this load in
+// vmcnt: the barrier that publishes the slice needs its own s_waitcnt vmcnt(0).
+__device__ __forceinline__ void glds16s(const char* ubase, uint32_t voff, void* lds_dst) {
+  const uint32_t dst = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void*)lds_dst);
+  asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(uniform_ptr(ubase)), "{m0}"(dst) : "memory");
+}
+
+#ifdef SMLU_CLOCK_PROBE
+// Dev build only (tools/gemm_clock.sh): where a slice of the interior K loop spends its cycles.
+// Every wave stamps s_memtime at the segment ends and keeps per-segment scalar sums; wave 0 of
+// workgroup 0 of an armed launch adds them to g_clock_probe[8 + 8 form + segment] (segment 6: slices,
+// 7: launches).  The stamp drains the wave's LDS reads, so the build reads shares, not run time.
+__device__ unsigned long long* g_clock_probe = nullptr;
+struct KloopStamps {
+  unsigned long long last, sum[6];
+  unsigned n;
+  static __device__ __forceinline__ unsigned long long now() {
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+  }
+  __device__ __forceinline__ void start() {
+    for (int b = 0; b < 6; ++b) sum[b] = 0;
+    n = 0;
+    last = now();
+  }
+  __device__ __forceinline__ void mark(int b) {
+    const unsigned long long t = now();
+    sum[b] += t - last;
+    last = t;
+    if (b == 5) ++n;
+  }
+  __device__ __forceinline__ void done(int form) const {
+    unsigned long long* p = g_clock_probe;
+    if (p && blockIdx.x == 0 && threadIdx.x == 0) {
+      for (int b = 0; b < 6; ++b) atomicAdd(p + 8 + 8 * form + b, sum[b]);
+      atomicAdd(p + 8 + 8 * form + 6, (unsigned long long)n);
+      atomicAdd(p + 8 + 8 * form + 7, 1ull);
+    }
+  }
+};
+// segments: the slice's quad 0 with the fragment reads and DMA pieces behind its MFMAs; quads 1-2;
+// the barrier with its vmcnt(0)/lgkmcnt(0); quad 3 with the next slice's first fragment reads.
+// (KS_DMA, KS_PBW: the DMA block at the slice top and the exposed reads behind the barrier of the
+// earlier loop form; zero now, kept so that reports of both forms read alike.)
+enum { KS_DMA = 0, KS_Q0 = 1, KS_Q12 = 2, KS_BAR = 3, KS_PBW = 4, KS_Q3 = 5 };
+#define KLOOP_DECL() KloopStamps ks
+#define KLOOP_START() ks.start()
+#define KLOOP_MARK(b) ks.mark(b)
+#define KLOOP_DONE(form) ks.done(form)
+#else
+#define KLOOP_DECL()
+#define KLOOP_START()
+#define KLOOP_MARK(b)
+#define KLOOP_DONE(form)
+#endif
 
 template <bool TRSM, bool EB, bool GATHER = false>
 __device__ __forceinline__ void gemm128_mfma3_interior(const GemmTask& t, int m0, int n0, Mfma3Lds& S,
@@ -481,6 +554,17 @@ __device__ __forceinline__ void gemm128_mfma3_interior(const GemmTask& t, int m0
       glds16(asrc + ((int64_t)(k0 + 4 * q) * lda) * 8, &S.A[buf][wv + 4 * q][0]);
       glds16(bsrc + ((int64_t)32 * q * ldb + k0) * 8, &S.B[buf][8 * (wv + 4 * q)][0]);
     }
+  };
+  // The same pieces one at a time (piece p of 8: A k-rows on even p, B columns on odd p), addressed
+  // as wave-uniform base + 32-bit lane offset so that the per-slice address arithmetic is scalar.
+  const char* asrc_u = reinterpret_cast<const char*>(t.A) + ((int64_t)wv * lda + m0) * 8;
+  const char* bsrc_u = reinterpret_cast<const char*>(t.B) + ((int64_t)(n0 + 8 * wv) * ldb) * 8;
+  const uint32_t a_lane = (uint32_t)lane * 16u;
+  const uint32_t b_lane = ((uint32_t)(lane >> 3) * (uint32_t)ldb + 2u * (uint32_t)bpair) * 8u;   // < 64 ldb
+  auto piece = [&](int k0, int buf, int p) {
+    const int q = p >> 1;
+    if (p & 1) glds16s(bsrc_u + ((int64_t)32 * q * ldb + k0) * 8, b_lane, &S.B[buf][8 * (wv + 4 * q)][0]);
+    else glds16s(asrc_u + ((int64_t)(k0 + 4 * q) * lda) * 8, a_lane, &S.A[buf][wv + 4 * q][0]);
   };
   auto stage_tail = [&](int k0, int buf) {   // partial slice: guarded register loads, zero fill
 #pragma unroll
@@ -551,67 +635,102 @@ __device__ __forceinline__ void gemm128_mfma3_interior(const GemmTask& t, int m0
 #pragma unroll
     for (int j = 0; j < 4; ++j) fb[j] = Bs[16 * HBK_ * j];
   };
-  auto quad = [&](const v2d (&fa)[2], const double (&fb)[4]) {
-#pragma unroll
-    for (int ip = 0; ip < 2; ++ip)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {   // neg:[1,0,0]: C - B*A
-        acc[2 * ip][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[j], fa[ip].x, acc[2 * ip][j], 0, 0, 1);
-        acc[2 * ip + 1][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[j], fa[ip].y, acc[2 * ip + 1][j], 0, 0, 1);
-      }
+  // MFMA n (0..15) of a k-quad: accumulator (2 ip + (n & 1), j) with ip = n >> 3, j = (n >> 1) & 3.
+  // Each accumulator takes exactly one MFMA per quad, quads in ascending k.   neg:[1,0,0]: C - B*A
+  auto mf = [&](int n, const v2d (&fa)[2], const double (&fb)[4]) {
+    const int ip = n >> 3, j = (n >> 1) & 3;
+    if (n & 1) acc[2 * ip + 1][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[j], fa[ip].y, acc[2 * ip + 1][j], 0, 0, 1);
+    else acc[2 * ip][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[j], fa[ip].x, acc[2 * ip][j], 0, 0, 1);
   };
-  auto slice = [&](int cur) {
-    v2d fa0[2], fa1[2];
-    double fb0[4], fb1[4];
-    frags(cur, 0, fa0, fb0);
-    frags(cur, 1, fa1, fb1);
-    quad(fa0, fb0);
-    frags(cur, 2, fa0, fb0);
-    quad(fa1, fb1);
-    frags(cur, 3, fa1, fb1);
-    quad(fa0, fb0);
-    quad(fa1, fb1);
+  auto rest = [&](const v2d (&fa)[2], const double (&fb)[4]) {   // MFMAs 1..15 of a quad
+#pragma unroll
+    for (int n = 1; n < 16; ++n) mf(n, fa, fb);
   };
+  // One slice.  The two fragment sets alternate by quad; the set that quad q + 1 needs is read right
+  // behind quad q's FIRST MFMA -- its registers were last used by quad q - 1, whose MFMAs have all
+  // been issued -- and waited for behind quad q's last one, 15 MFMAs later.  The next slice's eight
+  // DMA pieces follow in pairs behind MFMAs 1, 3, 5 and 7 of quad 0 (their buffer is free since the
+  // previous barrier), the last pair 40 MFMAs ahead of the vmcnt(0) in front of the barrier between
+  // quads 2 and 3; behind that barrier come quad 3's first MFMA and only then the next slice's
+  // quad-0 fragments.  The scheduling fences pin this order: every group of non-MFMA work has an
+  // MFMA of this wave in flight.  The barrier and the reads behind it run on the last slice too (the
+  // reads fetch stale LDS that nothing uses), so the loop body has no join that carries LDS reads:
+  // only the DMA pieces and the partial slice's register staging sit under (uniform) branches.
+  // Two slices per loop trip make the LDS buffer a compile-time constant, so every fragment address
+  // is one per-lane register plus an immediate; with the scalar-base DMA form the loop has no
+  // vector ALU instruction besides the MFMAs (each one costs the wave an issue slot it has to win
+  // against the other workgroup's wave on the same SIMD).
   const int nk = (K + HBK_ - 1) / HBK_;
   const int nfull = K / HBK_;
+  v2d fa0[2], fa1[2];
+  double fb0[4], fb1[4];
+  auto lds_wait = [] {   // s_waitcnt lgkmcnt(0) alone, in its place
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_sched_barrier(0);
+  };
   if (nfull > 0) issue(0, 0);
   else stage_tail(0, 0);
   __syncthreads();
-  if (!EB) {
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      const bool next = kt + 1 < nk;
-      const bool next_full = kt + 1 < nfull;
-      if (next_full) issue((kt + 1) * HBK_, cur ^ 1);
-      if (next && !next_full) stage_tail((kt + 1) * HBK_, cur ^ 1);
-      slice(cur);
-      if (next) __syncthreads();
-    }
-  } else {
-    // the next slice's barrier between k-quads 2 and 3 (all of this slice's fragments are in
-    // registers by then) and its first fragments read behind quad 3's MFMAs
-    v2d fa0[2], fa1[2];
-    double fb0[4], fb1[4];
-    frags(0, 0, fa0, fb0);
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      const bool next = kt + 1 < nk;
-      const bool next_full = kt + 1 < nfull;
-      if (next_full) issue((kt + 1) * HBK_, cur ^ 1);
-      if (next && !next_full) stage_tail((kt + 1) * HBK_, cur ^ 1);
-      frags(cur, 1, fa1, fb1);
-      quad(fa0, fb0);
-      frags(cur, 2, fa0, fb0);
-      quad(fa1, fb1);
-      frags(cur, 3, fa1, fb1);
-      quad(fa0, fb0);
-      if (next) {
-        __syncthreads();
-        frags(cur ^ 1, 0, fa0, fb0);
+  frags(0, 0, fa0, fb0);
+  lds_wait();
+  KLOOP_DECL();
+  KLOOP_START();
+  auto body = [&](int kt, auto cur_c) {
+    constexpr int cur = decltype(cur_c)::value;
+    const int k1 = (kt + 1) * HBK_;
+    const bool next_full = kt + 1 < nfull;
+    mf(0, fa0, fb0);
+    __builtin_amdgcn_sched_barrier(0);
+    frags(cur, 1, fa1, fb1);
+    if (kt + 1 < nk && !next_full) stage_tail(k1, cur ^ 1);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int n = 1; n < 16; ++n) {
+      mf(n, fa0, fb0);
+      if ((n & 1) && n < 8) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (next_full) {
+          piece(k1, cur ^ 1, n - 1);
+          piece(k1, cur ^ 1, n);
+        }
+        __builtin_amdgcn_sched_barrier(0);
       }
-      quad(fa1, fb1);
     }
+    lds_wait();
+    KLOOP_MARK(KS_Q0);
+    mf(0, fa1, fb1);
+    __builtin_amdgcn_sched_barrier(0);
+    frags(cur, 2, fa0, fb0);
+    __builtin_amdgcn_sched_barrier(0);
+    rest(fa1, fb1);
+    lds_wait();
+    mf(0, fa0, fb0);
+    __builtin_amdgcn_sched_barrier(0);
+    frags(cur, 3, fa1, fb1);
+    __builtin_amdgcn_sched_barrier(0);
+    rest(fa0, fb0);
+    KLOOP_MARK(KS_Q12);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(0x0070);   // vmcnt(0) lgkmcnt(0): this wave's DMA pieces have landed
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
+    KLOOP_MARK(KS_BAR);
+    mf(0, fa1, fb1);
+    __builtin_amdgcn_sched_barrier(0);
+    frags(cur ^ 1, 0, fa0, fb0);
+    __builtin_amdgcn_sched_barrier(0);
+    rest(fa1, fb1);
+    lds_wait();
+    KLOOP_MARK(KS_Q3);
+  };
+  for (int kt = 0;; kt += 2) {   // two slices per trip: the LDS buffer is a compile-time constant
+    body(kt, std::integral_constant<int, 0>{});
+    if (kt + 1 >= nk) break;
+    body(kt + 1, std::integral_constant<int, 1>{});
+    if (kt + 2 >= nk) break;
   }
+  KLOOP_DONE(EB ? 0 : 1);
   double gmax = 0.0;
 #pragma unroll
   for (int ip = 0; ip < 2; ++ip)
@@ -857,7 +976,6 @@ __device__ __forceinline__ void gemm128_mfma3_edge(const GemmTask& t, int m0, in
 // workgroup's own counters -- sum of delta s_memtime (shader cycles) and of delta s_memrealtime
 // (100 MHz constant clock) over every workgroup of the armed launches, per form (EB = F22, else
 // trailing/in-block), accumulated by vector atomics from lane 0.
-__device__ unsigned long long* g_clock_probe = nullptr;
 struct ClockMark {
   unsigned long long t0, r0;
   __device__ __forceinline__ ClockMark() : t0(__builtin_amdgcn_s_memtime()), r0(__builtin_amdgcn_s_memrealtime()) {}
@@ -1129,17 +1247,18 @@ __global__ __launch_bounds__(256) void k_tri_inv(const int32_t* __restrict__ lis
 }
 
 #ifdef SMLU_CLOCK_PROBE
-// arm != 0: zero the counters and arm the probe; arm == 0: copy the 8 counters out and disarm
+// arm != 0: zero the counters and arm the probe; arm == 0: copy the 24 counters out (8 clock sums,
+// then 8 K-loop stamp sums per form) and disarm
 extern "C" int smlu_dev_gemm_clock(int arm, unsigned long long* out) {
   static unsigned long long* buf = nullptr;
-  if (!buf && hipMalloc(&buf, 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
+  if (!buf && hipMalloc(&buf, 24 * sizeof(unsigned long long)) != hipSuccess) return -1;
   unsigned long long* p = nullptr;
   if (arm) {
-    if (hipMemset(buf, 0, 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    if (hipMemset(buf, 0, 24 * sizeof(unsigned long long)) != hipSuccess) return -1;
     p = buf;
   } else {
     if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (out && hipMemcpy(out, buf, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (out && hipMemcpy(out, buf, 24 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
   }
   return hipMemcpyToSymbol(HIP_SYMBOL(g_clock_probe), &p, sizeof p) == hipSuccess ? 0 : -1;
 }

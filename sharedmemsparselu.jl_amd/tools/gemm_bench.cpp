@@ -7,6 +7,11 @@
 #include <vector>
 #include "../csrc/device.hpp"
 namespace smlu { hipError_t launch_gemm(hipStream_t, int64_t, const GemmTask*, int, int, int64_t); }
+#ifdef SMLU_CLOCK_PROBE
+// the clock-probe build (tools/gemm_clock.sh): per 128-tile variant also the K-loop stamps of
+// workgroup 0, cycles per slice by segment (kernels_gemm.hip, KloopStamps)
+extern "C" int smlu_dev_gemm_clock(int arm, unsigned long long* out);
+#endif
 using namespace smlu;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP %s at %s\n", hipGetErrorString(e), #x); exit(1);} } while (0)
 
@@ -73,11 +78,29 @@ int main(int argc, char** argv) {
           for (size_t o = 0; o < r.size(); ++o) vdiff[variant] = fmax(vdiff[variant], fabs(r[o] - ref[o]));
       }
       int reps = (double)m * n * k > 1e11 ? 3 : 20;
+#ifdef SMLU_CLOCK_PROBE
+      if (smlu_dev_gemm_clock(1, nullptr) != 0) { printf("clock probe: arm failed\n"); exit(1); }
+#endif
       CK(hipEventRecord(e0, st));
       for (int r = 0; r < reps; ++r) CK(launch_gemm(st, tiles, dt, 1, tile, 0));
       CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
       float ms; CK(hipEventElapsedTime(&ms, e0, e1));
       res[variant] = 2.0 * m * n * (double)k * reps / (ms * 1e-3) / 1e12;
+#ifdef SMLU_CLOCK_PROBE
+      {
+        unsigned long long c[24];
+        if (smlu_dev_gemm_clock(0, c) != 0) { printf("clock probe: read failed\n"); exit(1); }
+        for (int form = 0; form < 2; ++form) {
+          const unsigned long long* s = c + 8 + 8 * form;
+          if (!s[6]) continue;
+          const double ns = (double)s[6];
+          printf("  stamps m=%d n=%d k=%d t%d: %llu slices of workgroup 0 (%llu launches), clock %.0f MHz; cycles per slice:"
+                 " dma %.0f | quad0 %.0f | quads1-2 %.0f | barrier %.0f | post-barrier reads %.0f | quad3 %.0f | sum %.0f\n",
+                 m, n, k, tile, s[6], s[7], c[4 * form + 1] ? 100.0 * c[4 * form] / c[4 * form + 1] : 0.0, s[0] / ns,
+                 s[1] / ns, s[2] / ns, s[3] / ns, s[4] / ns, s[5] / ns, (s[0] + s[1] + s[2] + s[3] + s[4] + s[5]) / ns);
+        }
+      }
+#endif
     }
     printf("m=%6d n=%6d k=%6d ld=%d,%d,%d ", m, n, k, lda, ldb, ldc);
     for (int v = 0; v < NV; ++v) printf(" t%d %6.2f TF (maxdiff vs t%d %.1e)", tiles_list[v], res[v], tiles_list[0], vdiff[v]);

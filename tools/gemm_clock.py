@@ -44,7 +44,7 @@ def main():
         smlu.lu_(F, A)
     ev1.record()
     torch.cuda.synchronize()
-    out = np.zeros(8, np.uint64)
+    out = np.zeros(24, np.uint64)   # 8 clock sums, then the K-loop stamp sums (tools/gemm_clock.sh)
     assert fn(0, out.ctypes.data) == 0
     res = {"side": args.side, "reps": args.reps, "refactor_ms": ev0.elapsed_time(ev1) / args.reps}
     for form, name in ((0, "f22"), (1, "trailing_inblock")):
