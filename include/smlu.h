@@ -160,8 +160,13 @@ int smlu_solve_multi_device(smlu_handle* h, int64_t nrhs, const double* d_B, int
  * stream (smlu_set_stream), iterative refinement by the same rule (residual b - A^T x with the
  * componentwise denominator |A^T||x| + |b|; "refine_steps" / "refine_berr"), "solve_ms_last" set.
  * Two solves of the same b are bitwise equal.  Single-GPU only: a partitioned handle (smlu_dist_*)
- * gives SMLU_ERR_STATE.  The _multi forms solve column by column on the single-vector path (no
- * batched transposed kernels). */
+ * gives SMLU_ERR_STATE.  The _multi forms (ldb, ldx >= n; X == B allowed when ldb == ldx) take the
+ * columns through the batched transposed kernels in batches of up to 16: each factor value is read
+ * once per batch, and column j of X is bitwise smlu_solve_trans_device of column j alone.  When
+ * refinement applies (see smlu_opts.refine) they run one refined transposed solve per column
+ * instead.  "solve_ms_last" is the sum over the batches (columns);  "solve_trans_passes" counts the
+ * transposed pass pairs (U^T then L^T) run on the handle so far, refinement corrections included:
+ * one per single-vector solve, one per batch of up to 16 columns. */
 #define SMLU_OP_N 0   /* A x = b   */
 #define SMLU_OP_T 1   /* A^T x = b */
 #define SMLU_OP_H 2   /* A^H x = b (real handle: same as T) */
@@ -268,7 +273,7 @@ int64_t     smlu_last_error_col(const smlu_handle* h);      /* column of a zero/
  * "n","nnzA","nsuper","nlevels","nnzL","nnzU","nnzLU","flops","upd","front_max","ns_max",
  * "factor_bytes","scratch_bytes","launches","analysis_ms","refactor_ms_last","solve_ms_last",
  * "growth_max","dense_flops","gemm_flops","ms_gemm","ms_panel","ms_trsm","ms_assemble",
- * "ms_small","ms_solve". Returns NaN for an unknown key. */
+ * "ms_small","ms_solve","solve_trans_passes". Returns NaN for an unknown key. */
 double smlu_stat(const smlu_handle* h, const char* key);
 
 /* ---- host-only symbolic analysis (no GPU needed; used by the CPU test suite) ------- */

@@ -87,23 +87,24 @@ hipError_t launch_bwd_u12_cols(hipStream_t, const SNode*, int, int64_t, int64_t,
                                const double*, const double*, double*);
 hipError_t launch_vcopy(hipStream_t, const SNode*, int, int64_t, const double*, double*);
 hipError_t launch_unswap(hipStream_t, int64_t, const int64_t*, const int32_t*, const double*, double*);
-// kernels_solve_t.hip: the transposed / adjoint solve
+// kernels_solve_t.hip: the transposed / adjoint solve (rh.n > 1: the batched kernels of kernels_solve_tb.hip)
 hipError_t launch_ut_tiny(hipStream_t, int, const int32_t*, const SNode*, const int32_t*, const int32_t*, const double*,
-                          double*, double*, int);
+                          double*, double*, Rhs, int);
 hipError_t launch_lt_tiny(hipStream_t, int, const int32_t*, const SNode*, const int32_t*, const int32_t*, const double*,
-                          double*, int);
+                          double*, Rhs, int);
 hipError_t launch_ut_front(hipStream_t, int, const int32_t*, const SNode*, const int32_t*, const int32_t*,
-                           const double*, double*, double*);
+                           const double*, double*, double*, Rhs);
 hipError_t launch_lt_front(hipStream_t, int, const int32_t*, const SNode*, const int32_t*, const int32_t*,
-                           const double*, double*, double*);
+                           const double*, double*, double*, Rhs);
 hipError_t launch_pull_t(hipStream_t, int64_t, const FrontTile*, int, const SNode*, const int32_t*, const int32_t*,
-                         const double*, double*);
+                         const double*, double*, Rhs);
 hipError_t launch_tri_t(hipStream_t, bool, int64_t, const FrontTile*, int, int, const SNode*, const int32_t*,
-                        const double*, double*, double*);
+                        const double*, double*, double*, Rhs);
 hipError_t launch_bwdu_t(hipStream_t, int64_t, const FrontTile*, int, const SNode*, const int32_t*, const double*,
-                         const double*, double*);
-hipError_t launch_perm_in_t(hipStream_t, int64_t, const int64_t*, const double*, double*, int);
-hipError_t launch_perm_out_t(hipStream_t, int64_t, const int64_t*, const double*, const double*, double*, int);
+                         const double*, double*, Rhs);
+hipError_t launch_perm_in_t(hipStream_t, int64_t, const int64_t*, const double*, int64_t, double*, int, Rhs);
+hipError_t launch_perm_out_t(hipStream_t, int64_t, const int64_t*, const double*, const double*, double*, int64_t,
+                             int, Rhs);
 hipError_t launch_residual_t(hipStream_t, int64_t, const int64_t*, const int32_t*, const double*, const double*,
                              const double*, double*, double*, int);
 }  // namespace smlu
@@ -239,6 +240,7 @@ struct smlu_handle {
   int64_t bad_info_node = -1, bad_info_count = 0;   // illegal info words seen by k_status
   int32_t bad_info_word = 0;
   int64_t sweep_timeouts = 0;   // solves re-run on the per-block schedule after a sweep wait timed out
+  int64_t trans_passes = 0;     // executions of the transposed pass pair (U^T then L^T), one per batch of columns
   int sweep_spin = 1 << 22;     // polls before a sweep wait gives up (SMLU_SWEEP_SPIN; 0 = always, tests)
   DBuf<double> bstash;          // the solve's input when the final step overwrites it (x === b, lsolve!/rsolve!)
   std::vector<std::pair<int, hipGraphExec_t>> sol_execs;   // captured solve sweeps, keyed by mode/rhs count

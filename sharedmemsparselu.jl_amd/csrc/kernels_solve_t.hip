@@ -9,54 +9,9 @@
 // atomics: two solves of the same b are bitwise equal).  The diagonal blocks are staged in LDS by
 // coalesced loads and read back transposed with an odd stride (no bank conflicts), one row per lane.
 // Every wait is stream order; no workgroup waits for another.
-#include "kernels_common.hpp"
+#include "kernels_solve_t.hpp"
 
 namespace smlu {
-
-// ---- dot products over contiguous runs: 16 lanes per run ------------------------------------
-// a[u] += sum over idx = e, e + 16, ... < len of ptr[u][idx] * xv[idx] (e = lane within the group):
-// four strides of 16 per round, the loads of a round issued before its fmas.
-template <int U>
-__device__ __forceinline__ void dots16(const double* const (&ptr)[U], const bool (&ok)[U], const double* xv,
-                                       int64_t len, int e, double (&a)[U]) {
-  for (int64_t i0 = 0; i0 < len; i0 += 64) {
-    double d[U][4], xx[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int64_t idx = i0 + e + 16 * k;
-      xx[k] = idx < len ? xv[idx] : 0.0;
-#pragma unroll
-      for (int u = 0; u < U; ++u) d[u][k] = (ok[u] && idx < len) ? ptr[u][idx] : 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int u = 0; u < U; ++u) a[u] = fma(d[u][k], xx[k], a[u]);
-  }
-}
-// sum over the 16 lanes of a group (every lane of the wave takes part), the same tree on every call
-__device__ __forceinline__ double red16(double a) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-  return a;
-}
-
-// Sixteen sums at once: lane e of a group holds partial sums a[0..15] of sixteen targets and leaves
-// with the group's total of target e (recursive halving: 8 + 4 + 2 + 1 exchanges instead of 16 x 4,
-// the additions of every target in the same fixed order on every call).
-__device__ __forceinline__ double red16x16(double (&a)[16], int e) {
-#pragma unroll
-  for (int h = 8; h > 0; h >>= 1) {
-    const bool up = (e & h) != 0;
-#pragma unroll
-    for (int i = 0; i < h; ++i) {
-      const double send = up ? a[i] : a[i + h];
-      const double keep = up ? a[i + h] : a[i];
-      a[i] = keep + __shfl_xor(send, h, 64);
-    }
-  }
-  return a[0];
-}
 
 // v[t] -= <col(t)[0 : bw), ys> for the targets t in [lo, hi): 16 groups of 16 lanes (256 threads),
 // four targets per group and round.  col(t) -> start of the target's contiguous run.
@@ -86,14 +41,6 @@ __device__ __forceinline__ void apply_dots(int64_t lo, int64_t hi, int bw, const
   }
 }
 
-// 64 x 64 diagonal block D (ld M) -> sD[col * 65 + row] by all 256 threads (coalesced along a column)
-__device__ __forceinline__ void stage_block_t(double* __restrict__ sD, const double* __restrict__ D, int64_t M,
-                                              int bw, int tid) {
-  for (int idx = tid; idx < bw * 64; idx += 256) {
-    const int i = idx & 63, j = idx >> 6;
-    if (i < bw) sD[j * 65 + i] = D[(int64_t)j * M + i];
-  }
-}
 // One wave solves the staged block transposed.  Row `lane` of the transposed block is the block's
 // column `lane`: sD[lane * 65 + j] (stride 65 across lanes).
 //   !UPPER: U11^T y = x, non-unit lower (entries j <= lane), ascending;
@@ -236,20 +183,6 @@ __global__ __launch_bounds__(256) void k_lt_front(const int32_t* __restrict__ li
 // fronts per workgroup, no workgroup barrier.  The triangle is staged 32 columns at a time into a
 // per-wave LDS tile T[col * 33 + row] (coalesced along the panel columns) and read back one panel
 // column per lane; the U12 / L21 products give G = 2^ceil(log2(len)) lanes to each contiguous run.
-constexpr int kTinyWaves = 2;
-__device__ __forceinline__ void stage_tile_t(double* __restrict__ T, const double* __restrict__ Lp, int M, int ns,
-                                             int c0, int cw, int lane) {
-  for (int idx = lane; idx < ns * 32; idx += 64) {
-    const int r = idx & 31, i = idx >> 5;
-    if (r < cw) T[i * 33 + r] = Lp[(int64_t)i * M + c0 + r];
-  }
-}
-__device__ __forceinline__ int pow2_at_least(int n) {
-  int g = 1;
-  while (g < n && g < 64) g <<= 1;
-  return g;
-}
-
 __global__ __launch_bounds__(64 * kTinyWaves) void k_ut_tiny(const int32_t* __restrict__ list, int cnt,
                                                              const SNode* __restrict__ sn,
                                                              const int32_t* __restrict__ chlist,
@@ -695,10 +628,13 @@ __global__ __launch_bounds__(256) void k_residual_t(int64_t n, const int64_t* __
 }
 
 // ---- host-side launch wrappers (solve.cpp) ---------------------------------------------------
+// One right-hand side runs the kernels above; a batch (rh.n > 1) their variants of
+// kernels_solve_tb.hip on the same lists and workgroup counts.
 static inline unsigned nblk_t(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 hipError_t launch_ut_tiny(hipStream_t st, int cnt, const int32_t* list, const SNode* sn, const int32_t* chlist,
-                          const int32_t* relmap, const double* store, double* x, double* vbuf, int micro) {
+                          const int32_t* relmap, const double* store, double* x, double* vbuf, Rhs rh, int micro) {
   if (cnt <= 0) return hipSuccess;
+  if (rh.n > 1) return launch_ut_tiny_b(st, cnt, list, sn, chlist, relmap, store, x, vbuf, rh, micro);
   if (micro) {   // every front of the list has M <= 8
     k_ut_micro<<<nblk_t(cnt, 32), 256, 0, st>>>(list, cnt, sn, chlist, relmap, store, x, vbuf);
     return hipGetLastError();
@@ -707,8 +643,9 @@ hipError_t launch_ut_tiny(hipStream_t st, int cnt, const int32_t* list, const SN
   return hipGetLastError();
 }
 hipError_t launch_lt_tiny(hipStream_t st, int cnt, const int32_t* list, const SNode* sn, const int32_t* rows,
-                          const int32_t* rowperm, const double* store, double* x, int micro) {
+                          const int32_t* rowperm, const double* store, double* x, Rhs rh, int micro) {
   if (cnt <= 0) return hipSuccess;
+  if (rh.n > 1) return launch_lt_tiny_b(st, cnt, list, sn, rows, rowperm, store, x, rh, micro);
   if (micro) {
     k_lt_micro<<<nblk_t(cnt, 32), 256, 0, st>>>(list, cnt, sn, rows, rowperm, store, x);
     return hipGetLastError();
@@ -717,44 +654,54 @@ hipError_t launch_lt_tiny(hipStream_t st, int cnt, const int32_t* list, const SN
   return hipGetLastError();
 }
 hipError_t launch_ut_front(hipStream_t st, int cnt, const int32_t* list, const SNode* sn, const int32_t* chlist,
-                           const int32_t* relmap, const double* store, double* x, double* vbuf) {
+                           const int32_t* relmap, const double* store, double* x, double* vbuf, Rhs rh) {
   if (cnt <= 0) return hipSuccess;
+  if (rh.n > 1) return launch_ut_front_b(st, cnt, list, sn, chlist, relmap, store, x, vbuf, rh);
   k_ut_front<<<cnt, 256, 0, st>>>(list, sn, chlist, relmap, store, x, vbuf);
   return hipGetLastError();
 }
 hipError_t launch_lt_front(hipStream_t st, int cnt, const int32_t* list, const SNode* sn, const int32_t* rows,
-                           const int32_t* rowperm, const double* store, double* x, double* vbuf) {
+                           const int32_t* rowperm, const double* store, double* x, double* vbuf, Rhs rh) {
   if (cnt <= 0) return hipSuccess;
+  if (rh.n > 1) return launch_lt_front_b(st, cnt, list, sn, rows, rowperm, store, x, vbuf, rh);
   k_lt_front<<<cnt, 256, 0, st>>>(list, sn, rows, rowperm, store, x, vbuf);
   return hipGetLastError();
 }
 hipError_t launch_pull_t(hipStream_t st, int64_t nwg, const FrontTile* ft, int nft, const SNode* sn,
-                         const int32_t* gptr, const int32_t* gent, const double* x, double* vbuf) {
+                         const int32_t* gptr, const int32_t* gent, const double* x, double* vbuf, Rhs rh) {
   if (nwg <= 0) return hipSuccess;
+  if (rh.n > 1) return launch_pull_tb(st, nwg, ft, nft, sn, gptr, gent, x, vbuf, rh);
   k_pull_t<<<(unsigned)nwg, 256, 0, st>>>(ft, nft, sn, gptr, gent, x, vbuf);
   return hipGetLastError();
 }
 hipError_t launch_tri_t(hipStream_t st, bool upper, int64_t nwg, const FrontTile* ft, int nft, int step,
-                        const SNode* sn, const int32_t* rowperm, const double* store, double* x, double* vbuf) {
+                        const SNode* sn, const int32_t* rowperm, const double* store, double* x, double* vbuf,
+                        Rhs rh) {
   if (nwg <= 0) return hipSuccess;
+  if (rh.n > 1) return launch_tri_tb(st, upper, nwg, ft, nft, step, sn, rowperm, store, x, vbuf, rh);
   if (upper) k_tri_t<true><<<(unsigned)nwg, 320, 0, st>>>(ft, nft, step, sn, rowperm, store, x, vbuf);
   else k_tri_t<false><<<(unsigned)nwg, 320, 0, st>>>(ft, nft, step, sn, rowperm, store, x, vbuf);
   return hipGetLastError();
 }
 hipError_t launch_bwdu_t(hipStream_t st, int64_t nwg, const FrontTile* ft, int nft, const SNode* sn,
-                         const int32_t* rows, const double* store, const double* x, double* vbuf) {
+                         const int32_t* rows, const double* store, const double* x, double* vbuf, Rhs rh) {
   if (nwg <= 0) return hipSuccess;
+  if (rh.n > 1) return launch_bwdu_tb(st, nwg, ft, nft, sn, rows, store, x, vbuf, rh);
   k_bwdu_t<<<(unsigned)nwg, 256, 0, st>>>(ft, nft, sn, rows, store, x, vbuf);
   return hipGetLastError();
 }
-hipError_t launch_perm_in_t(hipStream_t st, int64_t n, const int64_t* q, const double* b, double* wrk, int conj) {
+// column j of b at b + j*ldb, of x at x + j*ldxo; of the work vectors at wrk + j*rh.ldx
+hipError_t launch_perm_in_t(hipStream_t st, int64_t n, const int64_t* q, const double* b, int64_t ldb, double* wrk,
+                            int conj, Rhs rh) {
   if (n <= 0) return hipSuccess;
+  if (rh.n > 1) return launch_perm_in_tb(st, n, q, b, ldb, wrk, conj, rh);
   k_perm_in_t<<<nblk_t(n, 256), 256, 0, st>>>(n, q, b, wrk, conj);
   return hipGetLastError();
 }
 hipError_t launch_perm_out_t(hipStream_t st, int64_t n, const int64_t* p0, const double* Rs, const double* wrk,
-                             double* x, int conj) {
+                             double* x, int64_t ldxo, int conj, Rhs rh) {
   if (n <= 0) return hipSuccess;
+  if (rh.n > 1) return launch_perm_out_tb(st, n, p0, Rs, wrk, x, ldxo, conj, rh);
   k_perm_out_t<<<nblk_t(n, 256), 256, 0, st>>>(n, p0, Rs, wrk, x, conj);
   return hipGetLastError();
 }

@@ -399,36 +399,45 @@ int smlu_solve_multi(smlu_handle* h, int64_t nrhs, const double* B, int64_t ldb,
 // launch by kind on the same work lists and workgroup counts; the schedule itself is untouched.
 // A ComplexF64 handle's K^T is the real equivalent of A^H: the same passes give the adjoint solve,
 // and the plain transpose is conj(A^H \ conj(b)), the conjugations folded into the permutations.
-static hipError_t run_solve_launch_t(smlu_handle* h, const Launch& L, double* w, double* v, hipStream_t st) {
+static hipError_t run_solve_launch_t(smlu_handle* h, const Launch& L, double* w, double* v, Rhs rh, hipStream_t st) {
   switch (L.kind) {
     case K_FWDT:
       return launch_ut_tiny(st, (int)L.cnt, h->ilist.p + L.off, h->sn.p, h->chlist.p, h->relmap.p, h->store.p, w, v,
-                            (int)L.aux);
+                            rh, (int)L.aux);
     case K_FWD:
-      return launch_ut_front(st, (int)L.cnt, h->ilist.p + L.off, h->sn.p, h->chlist.p, h->relmap.p, h->store.p, w, v);
+      return launch_ut_front(st, (int)L.cnt, h->ilist.p + L.off, h->sn.p, h->chlist.p, h->relmap.p, h->store.p, w, v,
+                             rh);
     case K_FWDP:
-      return launch_pull_t(st, L.nwg, h->ftiles.p + L.off, (int)L.cnt, h->sn.p, h->gptr.p, h->gent.p, w, v);
+      return launch_pull_t(st, L.nwg, h->ftiles.p + L.off, (int)L.cnt, h->sn.p, h->gptr.p, h->gent.p, w, v, rh);
     case K_TRIF:
       return launch_tri_t(st, false, L.nwg, h->ftiles.p + L.off, (int)L.cnt, L.step, h->sn.p, h->rowperm.p,
-                          h->store.p, w, v);
+                          h->store.p, w, v, rh);
     case K_BWDT:
       return launch_lt_tiny(st, (int)L.cnt, h->ilist.p + L.off, h->sn.p, h->rows.p, h->rowperm.p, h->store.p, w,
-                            (int)L.aux);
+                            rh, (int)L.aux);
     case K_BWD:
-      return launch_lt_front(st, (int)L.cnt, h->ilist.p + L.off, h->sn.p, h->rows.p, h->rowperm.p, h->store.p, w, v);
+      return launch_lt_front(st, (int)L.cnt, h->ilist.p + L.off, h->sn.p, h->rows.p, h->rowperm.p, h->store.p, w, v,
+                             rh);
     case K_BWDU:
-      return launch_bwdu_t(st, L.nwg, h->ftiles.p + L.off, (int)L.cnt, h->sn.p, h->rows.p, h->store.p, w, v);
+      return launch_bwdu_t(st, L.nwg, h->ftiles.p + L.off, (int)L.cnt, h->sn.p, h->rows.p, h->store.p, w, v, rh);
     case K_TRIB:
       return launch_tri_t(st, true, L.nwg, h->ftiles.p + L.off, (int)L.cnt, L.step, h->sn.p, h->rowperm.p,
-                          h->store.p, w, v);
+                          h->store.p, w, v, rh);
   }
   return hipErrorInvalidValue;   // no transposed meaning (the sequences of a one-GPU handle hold none)
 }
 
-constexpr int kTransGraphKey = 1 << 12;   // sol_execs key of the transposed passes (forward: mode * 256 + rhs)
+// sol_execs keys of the transposed passes: kTransGraphKey + columns in the batch (forward: mode * 256 + rhs)
+constexpr int kTransGraphKey = 1 << 12;
 
-static int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* dx) {
+// One pass pair for nrhs <= kMultiRhs columns of db / dx (leading dimensions ldb / ldx; one column:
+// unused).  A batch runs in wrkm / vbufm, the forward batch's buffers (calls on one handle are
+// serialised); db may alias dx when ldb == ldx: the whole batch is permuted into the work buffer
+// before any x is written.
+static int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* dx, int nrhs = 1, int64_t ldb = 0,
+                           int64_t ldx = 0) {
   Plan& P = h->plan;
+  if (nrhs < 1 || nrhs > kMultiRhs) return fail(h, SMLU_ERR_STATE, "transposed batch: 1 to 16 right-hand sides");
   hipStream_t st = h->stream;
   auto t0 = std::chrono::steady_clock::now();
   Timer tm(h);
@@ -436,7 +445,15 @@ static int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* d
   HIPCHK(tm.begin(K_FWD, &stop, st));
   double* w = h->wrk.p;
   double* v = h->vbuf.p;
-  HIPCHK(launch_perm_in_t(st, P.n, h->q.p, db, w, conj));
+  Rhs rh{1, (int64_t)P.n, (int64_t)h->vbuf.n};
+  if (nrhs > 1) {
+    if (!h->vbufm.p) HIPCHK(h->vbufm.alloc(h->vbuf.n * kMultiRhs));
+    if (!h->wrkm.p) HIPCHK(h->wrkm.alloc((size_t)P.n * kMultiRhs));
+    w = h->wrkm.p;
+    v = h->vbufm.p;
+    rh.n = nrhs;
+  }
+  HIPCHK(launch_perm_in_t(st, P.n, h->q.p, db, ldb, w, conj, rh));
   // a level's side launches on the side stream, forked after everything before the level and joined
   // before the next level -- and on the error path, so a failed launch never leaves the side stream
   // unjoined (inside a capture that would invalidate it)
@@ -452,7 +469,7 @@ static int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* d
         if (e == hipSuccess) e = hipStreamWaitEvent(h->side, h->fork_ev, 0);
         forked = e == hipSuccess;
       }
-      if (e == hipSuccess) e = run_solve_launch_t(h, L, w, v, L.side && forked ? h->side : st);
+      if (e == hipSuccess) e = run_solve_launch_t(h, L, w, v, rh, L.side && forked ? h->side : st);
       if (e == hipSuccess && last && forked) {
         e = hipEventRecord(h->join_ev, h->side);
         if (e == hipSuccess) e = hipStreamWaitEvent(st, h->join_ev, 0);
@@ -470,11 +487,13 @@ static int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* d
     int rc = run_seq(h->sch.fwdm);
     return rc != SMLU_OK ? rc : run_seq(h->sch.bwdm);
   };
-  // the two passes (fixed pointers: the handle's wrk / vbuf) captured once into a hipGraph and replayed
+  // the two passes (fixed pointers: the handle's wrk / vbuf, or wrkm / vbufm) captured once per batch
+  // width into a hipGraph and replayed
+  const int key = kTransGraphKey + rh.n;
   hipGraphExec_t ex = nullptr;
   if (!tune().no_graph && !h->graph_failed) {
     for (auto& g : h->sol_execs)
-      if (g.first == kTransGraphKey) ex = g.second;
+      if (g.first == key) ex = g.second;
     if (!ex) {
       hipGraph_t g = nullptr;
       HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
@@ -487,7 +506,7 @@ static int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* d
         h->graph_failed = true;
         ex = nullptr;
       } else {
-        h->sol_execs.push_back({kTransGraphKey, ex});
+        h->sol_execs.push_back({key, ex});
       }
     }
   }
@@ -496,7 +515,8 @@ static int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* d
     int rc = passes();
     if (rc != SMLU_OK) return rc;
   }
-  HIPCHK(launch_perm_out_t(st, P.n, h->p0.p, h->Rs.p, w, dx, conj));
+  ++h->trans_passes;
+  HIPCHK(launch_perm_out_t(st, P.n, h->p0.p, h->Rs.p, w, dx, ldx, conj, rh));
   HIPCHK(tm.end(stop));
   HIPCHK(hipStreamSynchronize(st));
   tm.collect();
@@ -583,7 +603,34 @@ int smlu_solve_trans(smlu_handle* h, int op, const double* b, double* x) {
   return SMLU_OK;
 }
 
-// Several right-hand sides: one transposed solve per column (no batched transposed kernels).
+// Several right-hand sides.  Without refinement, batches of up to kMultiRhs columns go through the
+// transposed kernels together (each factor value read once per batch; every column bitwise its
+// single-vector solve); otherwise one refined transposed solve per column.  d_B may alias d_X when
+// ldb == ldx.
+static int solve_trans_multi_dev(smlu_handle* h, int conj, int64_t nrhs, const double* d_B, int64_t ldb, double* d_X,
+                                 int64_t ldx) {
+  double ms = 0;
+  if (auto_refine_steps(h) != 0 || nrhs <= 1) {
+    for (int64_t j = 0; j < nrhs; ++j) {
+      int rc = solve_refined_t(h, conj, d_B + j * ldb, d_X + j * ldx);
+      if (rc != SMLU_OK) return rc;
+      ms += h->solve_ms;
+    }
+  } else {
+    h->refine_steps = 0;
+    h->refine_resid = -1;
+    h->refine_berr = -1;
+    for (int64_t j = 0; j < nrhs; j += kMultiRhs) {
+      const int nb = (int)std::min<int64_t>(kMultiRhs, nrhs - j);
+      int rc = run_solve_t_dev(h, conj, d_B + j * ldb, d_X + j * ldx, nb, ldb, ldx);
+      if (rc != SMLU_OK) return rc;
+      ms += h->solve_ms;
+    }
+  }
+  if (nrhs > 0) h->solve_ms = ms;
+  return SMLU_OK;
+}
+
 int smlu_solve_trans_multi_device(smlu_handle* h, int op, int64_t nrhs, const double* d_B, int64_t ldb, double* d_X,
                                   int64_t ldx) {
   if (!h || nrhs < 0 || (nrhs > 0 && (!d_B || !d_X))) return fail(h, SMLU_ERR_ARG, "invalid arguments");
@@ -595,14 +642,7 @@ int smlu_solve_trans_multi_device(smlu_handle* h, int op, int64_t nrhs, const do
   if (ldb < n || ldx < n) return fail(h, SMLU_ERR_ARG, "leading dimension smaller than n");
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(after_caller(h));
-  double ms = 0;
-  for (int64_t j = 0; j < nrhs; ++j) {
-    rc = solve_refined_t(h, conj, d_B + j * ldb, d_X + j * ldx);
-    if (rc != SMLU_OK) return rc;
-    ms += h->solve_ms;
-  }
-  if (nrhs > 0) h->solve_ms = ms;
-  return SMLU_OK;
+  return solve_trans_multi_dev(h, conj, nrhs, d_B, ldb, d_X, ldx);
 }
 
 int smlu_solve_trans_multi(smlu_handle* h, int op, int64_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx) {
@@ -615,6 +655,23 @@ int smlu_solve_trans_multi(smlu_handle* h, int op, int64_t nrhs, const double* B
   if (ldb < n || ldx < n) return fail(h, SMLU_ERR_ARG, "leading dimension smaller than n");
   HIPCHK(hipSetDevice(h->device));
   double ms = 0;
+  if (nrhs > 1 && auto_refine_steps(h) == 0) {   // batches staged through wrk2m, as smlu_solve_multi
+    if (!h->wrk2m.p) HIPCHK(h->wrk2m.alloc((size_t)n * kMultiRhs));
+    double* d = h->wrk2m.p;
+    for (int64_t j = 0; j < nrhs; j += kMultiRhs) {
+      const int64_t nb = std::min<int64_t>(kMultiRhs, nrhs - j);
+      HIPCHK(hipMemcpy2DAsync(d, sizeof(double) * n, B + j * ldb, sizeof(double) * ldb, sizeof(double) * n, nb,
+                              hipMemcpyHostToDevice, h->stream));
+      rc = solve_trans_multi_dev(h, conj, nb, d, n, d, n);
+      if (rc != SMLU_OK) return rc;
+      ms += h->solve_ms;
+      HIPCHK(hipMemcpy2DAsync(X + j * ldx, sizeof(double) * ldx, d, sizeof(double) * n, sizeof(double) * n, nb,
+                              hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->solve_ms = ms;
+    return SMLU_OK;
+  }
   for (int64_t j = 0; j < nrhs; ++j) {
     HIPCHK(hipMemcpyAsync(h->wrk2.p, B + j * ldb, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
     rc = solve_refined_t(h, conj, h->wrk2.p, h->wrk2.p);

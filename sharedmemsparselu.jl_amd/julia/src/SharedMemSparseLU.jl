@@ -174,7 +174,7 @@ function _ldiv_trans!(op::Int32, x::AbstractVecOrMat, F::ParallelSparseLU{Tf}, b
     if ndims(b) == 1
         check(ccall((:smlu_solve_trans, libsmlu), Int32, (Ptr{Cvoid}, Int32, Ptr{Tf}, Ptr{Tf}),
                     F.handle, op, bb, xx), F.handle)
-    else                                       # several right-hand sides: column by column in the library
+    else                                       # several right-hand sides: batches of 16 in the library
         ld = (Tf === ComplexF64 ? 2 : 1) * F.n  # leading dimension in doubles
         check(ccall((:smlu_solve_trans_multi, libsmlu), Int32,
                     (Ptr{Cvoid}, Int32, Int64, Ptr{Tf}, Int64, Ptr{Tf}, Int64),

@@ -299,8 +299,10 @@ class ParallelSparseLU:
     def solve_multi_device(self, d_X, d_B, trans="N"):
         """ldiv! for several right-hand sides on the device: d_B, d_X are (nrhs, n) contiguous
         torch tensors (column r = row r, i.e. column-major n x nrhs).  One GPU: batches of up to
-        16 columns go through the solve kernels together.  trans="T" / "C": one transposed /
-        adjoint solve per column (smlu_solve_trans_multi_device)."""
+        16 columns go through the solve kernels together.  trans="T" / "C": the transposed /
+        adjoint solve, also in batches of up to 16 columns, every column bitwise equal to
+        solve_device(..., trans=...) of that column alone; one refined solve per column when
+        iterative refinement applies (smlu_solve_trans_multi_device)."""
         op = _op(trans)
         nrhs, n = d_B.shape
         if n != self.n or tuple(d_X.shape) != (nrhs, n):
@@ -360,7 +362,9 @@ def lu_(F: ParallelSparseLU, A):
 def ldiv_(x, F: ParallelSparseLU, b, trans="N"):
     """ldiv!(x, F, b) — src/SharedMemSparseLU.jl:286-342.  ``x is b`` is allowed.
     trans="T" solves ``A.T x = b`` and trans="C" ``A.conj().T x = b`` from the same factors
-    (Julia's ``ldiv!(x, transpose(F), b)`` / ``ldiv!(x, F', b)``; smlu_solve_trans*)."""
+    (Julia's ``ldiv!(x, transpose(F), b)`` / ``ldiv!(x, F', b)``; smlu_solve_trans*).  2D ``x`` / ``b``
+    (columns) are solved in batches of up to 16 in either direction; a transposed batch gives every
+    column bitwise its single-vector result."""
     op = _op(trans)
     if F.m != F.n:
         raise DimensionMismatch(f"`F` is not square: F.m={F.m}, F.n={F.n}")

@@ -11,6 +11,13 @@ solves each, median over all of them; host clock around a solve that ends in a d
 synchronise, clocks as the device runs them (no pinning).
 
     python tools/solve_timing.py --trans [--side 128] [--reps 5]
+
+--trans --nrhs K: the same protocol for K columns, the batched transposed solve
+(solve_multi_device(..., trans="T")) against the forward solve_multi_device of the same columns on
+the per-block sequences; prints both times, the ratio and the number of transposed pass pairs one
+call took (K on a library that solves column by column, ceil(K / 16) with the batched kernels).
+
+    python tools/solve_timing.py --trans --nrhs 8 [--side 128] [--reps 5]
 """
 import argparse
 import os
@@ -27,6 +34,7 @@ def main():
     ap.add_argument("--side", type=int, default=128)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--trans", action="store_true")
+    ap.add_argument("--nrhs", type=int, default=1, help="with --trans: columns per solve")
     args = ap.parse_args()
     if args.trans:
         os.environ["SMLU_SOLVE_STEPS"] = "1"   # read when the handle's schedule is built
@@ -58,6 +66,12 @@ def main():
         xt = torch.empty_like(b)
         fwd = lambda: F.solve_device(x, b)
         trn = lambda: F.solve_device(xt, b, trans="T")
+        if args.nrhs > 1:
+            out["nrhs"] = args.nrhs
+            B = torch.from_numpy(rng.random((args.nrhs, n))).to(dev)
+            X, Xt = torch.empty_like(B), torch.empty_like(B)
+            fwd = lambda: F.solve_multi_device(X, B)
+            trn = lambda: F.solve_multi_device(Xt, B, trans="T")
         ts = {"fwd": [], "trans": []}
         for fn in (fwd, trn):   # warm-up: code objects, the captured graphs
             for _ in range(2):
@@ -74,6 +88,13 @@ def main():
             out[f"ms_{key}"] = float(np.median(v))
             out[f"ms_{key}_min_max"] = (float(min(v)), float(max(v)))
         out["ratio_trans_fwd"] = out["ms_trans"] / out["ms_fwd"]
+        if args.nrhs > 1:
+            passes = F.stat("solve_trans_passes")   # NaN on a library without the counter
+            trn()
+            out["trans_passes_per_call"] = F.stat("solve_trans_passes") - passes
+            F.solve_device(xt, B[-1].contiguous(), trans="T")
+            assert torch.equal(xt, Xt[-1])          # the last column is the single-vector solve, bitwise
+            b, x = B[-1].contiguous(), X[-1]
         bh, xh = b.cpu().numpy(), xt.cpu().numpy()
         out["resid_trans"] = float(np.abs(A.T @ xh - bh).max() / np.abs(bh).max())
         out["resid_fwd"] = float(np.abs(A @ x.cpu().numpy() - bh).max() / np.abs(bh).max())
