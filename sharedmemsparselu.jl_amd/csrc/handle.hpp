@@ -87,7 +87,7 @@ hipError_t launch_bwd_u12_cols(hipStream_t, const SNode*, int, int64_t, int64_t,
                                const double*, const double*, double*);
 hipError_t launch_vcopy(hipStream_t, const SNode*, int, int64_t, const double*, double*);
 hipError_t launch_unswap(hipStream_t, int64_t, const int64_t*, const int32_t*, const double*, double*);
-// kernels_solve_t.hip: the transposed / adjoint solve (rh.n > 1: the batched kernels of kernels_solve_tb.hip)
+// kernels_solve_t.hip: the transposed / adjoint solve (each launcher picks the batch width from rh.n)
 hipError_t launch_ut_tiny(hipStream_t, int, const int32_t*, const SNode*, const int32_t*, const int32_t*, const double*,
                           double*, double*, Rhs, int);
 hipError_t launch_lt_tiny(hipStream_t, int, const int32_t*, const SNode*, const int32_t*, const int32_t*, const double*,

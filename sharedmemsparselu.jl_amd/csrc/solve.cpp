@@ -45,6 +45,70 @@ static hipError_t run_solve_launch(smlu_handle* h, const Launch& L, double* w, d
   return hipErrorInvalidValue;
 }
 
+// The launches [lo, hi) of a sequence in order, launch(L, stream) for each.  overlap: a level's side
+// launches (grp > 0, side) go on the side stream, forked after everything before the level and
+// joined before the next level -- and on the error path, so a failed launch never leaves the side
+// stream unjoined (inside a capture that would invalidate it).
+template <class F>
+static hipError_t walk_launches(smlu_handle* h, const std::vector<Launch>& seq, size_t lo, size_t hi, bool overlap,
+                                F&& launch) {
+  hipStream_t st = h->stream;
+  bool forked = false;
+  hipError_t e = hipSuccess;
+  for (size_t i = lo; i < hi && e == hipSuccess; ++i) {
+    const Launch& L = seq[i];
+    const bool first = overlap && L.grp > 0 && (i == lo || seq[i - 1].grp != L.grp);
+    const bool last = overlap && L.grp > 0 && (i + 1 == hi || seq[i + 1].grp != L.grp);
+    if (first) {
+      e = hipEventRecord(h->fork_ev, st);
+      if (e == hipSuccess) e = hipStreamWaitEvent(h->side, h->fork_ev, 0);
+      forked = e == hipSuccess;
+    }
+    if (e == hipSuccess) e = launch(L, L.side && forked ? h->side : st);
+    if (e == hipSuccess && last && forked) {
+      e = hipEventRecord(h->join_ev, h->side);
+      if (e == hipSuccess) e = hipStreamWaitEvent(st, h->join_ev, 0);
+      if (e == hipSuccess) forked = false;
+    }
+  }
+  if (forked) {
+    (void)hipEventRecord(h->join_ev, h->side);
+    (void)hipStreamWaitEvent(st, h->join_ev, 0);
+  }
+  return e;
+}
+
+// body()'s launches on the handle's stream (fixed pointers: the handle's work buffers), captured once
+// per key into a hipGraph (h->sol_execs) and replayed.  A capture or instantiation that fails sets
+// graph_failed, and body() then runs eagerly, as it does when use_graph is false.
+template <class F>
+static int run_graphed(smlu_handle* h, bool use_graph, int key, F&& body) {
+  hipStream_t st = h->stream;
+  hipGraphExec_t ex = nullptr;
+  if (use_graph && !h->graph_failed) {
+    for (auto& g : h->sol_execs)
+      if (g.first == key) ex = g.second;
+    if (!ex) {
+      hipGraph_t g = nullptr;
+      HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+      int rc = body();
+      hipError_t ec = hipStreamEndCapture(st, &g);
+      if (rc == SMLU_OK && ec == hipSuccess && g) ec = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+      if (g) (void)hipGraphDestroy(g);
+      if (rc != SMLU_OK || ec != hipSuccess || !ex) {
+        (void)hipGetLastError();
+        h->graph_failed = true;
+        ex = nullptr;
+      } else {
+        h->sol_execs.push_back({key, ex});
+      }
+    }
+  }
+  if (!ex) return body();
+  HIPCHK(hipGraphLaunch(ex, st));
+  return SMLU_OK;
+}
+
 static int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode, int nrhs = 1, int64_t ldb = 0,
                          int64_t ldx = 0) {
   // mode 0: ldiv (b -> x); 1: lsolve in place on dx (final order); 2: rsolve in place.
@@ -100,6 +164,7 @@ static int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode,
   // overlap: a level's small fronts on the side stream next to its large fronts' per-block chain
   // (batched right-hand sides: 8 per 128^3 solve 59.5 -> 57.4 ms).  Not next to the sync-free
   // sweeps, whose waiting workgroups lose CUs to them (1 rhs: 13.8 -> 15.2 ms, round 6).
+  auto launch = [&](const Launch& L, hipStream_t s) { return run_solve_launch(h, L, w, v, rh, s); };
   auto run_seq = [&](const std::vector<Launch>& seq, const std::vector<size_t>& seg, const std::vector<int>& cm,
                      bool overlap) {
     for (size_t k = 0; k < seg.size(); ++k) {
@@ -108,25 +173,7 @@ static int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode,
         if (rc != SMLU_OK) return rc;
       }
       const size_t hi = k + 1 < seg.size() ? seg[k + 1] : seq.size();
-      // a level's side launches (grp > 0, side) on the side stream: forked after everything
-      // before the level, joined before the next level
-      bool forked = false;
-      for (size_t i = seg[k]; i < hi; ++i) {
-        const Launch& L = seq[i];
-        const bool first = overlap && L.grp > 0 && (i == seg[k] || seq[i - 1].grp != L.grp);
-        const bool last = overlap && L.grp > 0 && (i + 1 == hi || seq[i + 1].grp != L.grp);
-        if (first) {
-          HIPCHK(hipEventRecord(h->fork_ev, st));
-          HIPCHK(hipStreamWaitEvent(h->side, h->fork_ev, 0));
-          forked = true;
-        }
-        HIPCHK(run_solve_launch(h, L, w, v, rh, L.side && forked ? h->side : st));
-        if (last && forked) {
-          HIPCHK(hipEventRecord(h->join_ev, h->side));
-          HIPCHK(hipStreamWaitEvent(st, h->join_ev, 0));
-          forked = false;
-        }
-      }
+      HIPCHK(walk_launches(h, seq, seg[k], hi, overlap, launch));
     }
     return (int)SMLU_OK;
   };
@@ -148,36 +195,8 @@ static int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode,
   // One GPU: the forward and backward sweeps (~1,400 launches at 128^3, fixed pointers: the
   // handle's wrk / vbuf) are captured once per (mode, rhs count) into a hipGraph and replayed;
   // only the permutation kernels see the caller's b and x.
-  const bool nograph = tune().no_graph;
-  if (h->nranks == 1 && !nograph && !h->graph_failed) {
-    const int key = mode * 256 + rh.n;
-    hipGraphExec_t ex = nullptr;
-    for (auto& g : h->sol_execs)
-      if (g.first == key) ex = g.second;
-    if (!ex) {
-      hipGraph_t g = nullptr;
-      HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-      int rc = sweeps(steps);
-      hipError_t ec = hipStreamEndCapture(st, &g);
-      if (rc == SMLU_OK && ec == hipSuccess && g) ec = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-      if (g) (void)hipGraphDestroy(g);
-      if (rc != SMLU_OK || ec != hipSuccess || !ex) {
-        (void)hipGetLastError();
-        h->graph_failed = true;
-        ex = nullptr;
-      } else {
-        h->sol_execs.push_back({key, ex});
-      }
-    }
-    if (ex) HIPCHK(hipGraphLaunch(ex, st));
-    else {
-      int rc = sweeps(steps);
-      if (rc != SMLU_OK) return rc;
-    }
-  } else {
-    int rc = sweeps(steps);
-    if (rc != SMLU_OK) return rc;
-  }
+  int rc = run_graphed(h, h->nranks == 1 && !tune().no_graph, mode * 256 + rh.n, [&] { return sweeps(steps); });
+  if (rc != SMLU_OK) return rc;
   HIPCHK(finish());
   HIPCHK(tm.end(stop));
   HIPCHK(hipStreamSynchronize(st));
@@ -193,7 +212,7 @@ static int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode,
       ++h->sweep_timeouts;
       HIPCHK(hipMemsetAsync(h->sstatus.p, 0, sizeof(int32_t), st));
       HIPCHK(load_input(rerun_src, rerun_ld));
-      int rc = sweeps(true);
+      rc = sweeps(true);
       if (rc != SMLU_OK) return rc;
       HIPCHK(finish());
       HIPCHK(hipStreamSynchronize(st));
@@ -241,27 +260,28 @@ static int auto_refine_steps(const smlu_handle* h) {
   return (h->weak > 0 || diag_pref) ? 3 : 0;
 }
 
-static int solve_refined(smlu_handle* h, const double* db, double* dx) {
+// The refined solve of either direction: solve(b, x) is one plain solve on device vectors,
+// residual(x, b, r, nrm) launches r = b - op(A) x with its two norms (k_residual's rule).
+template <class SOLVE, class RESID>
+static int solve_refined_by(smlu_handle* h, const double* db, double* dx, SOLVE&& solve, RESID&& residual) {
   const int steps = auto_refine_steps(h);
   h->refine_steps = 0;
   h->refine_resid = -1;
   h->refine_berr = -1;
-  if (steps == 0) return run_solve_dev(h, db, dx, 0);
-  Plan& P = h->plan;
-  const int64_t n = P.n;
+  if (steps == 0) return solve(db, dx);
+  const int64_t n = h->plan.n;
   hipStream_t st = h->stream;
-  int rc0 = ensure_residual(h);
-  if (rc0 != SMLU_OK) return rc0;
+  int rc = ensure_residual(h);
+  if (rc != SMLU_OK) return rc;
   HIPCHK(hipMemcpyAsync(h->ref_b.p, db, sizeof(double) * n, hipMemcpyDeviceToDevice, st));   // db may alias dx
-  int rc = run_solve_dev(h, h->ref_b.p, dx, 0);
+  rc = solve(h->ref_b.p, dx);
   if (rc != SMLU_OK) return rc;
   const double ms = h->solve_ms;
   const double eps = std::ldexp(1.0, -51);   // 4 unit roundoffs
   double prev = HUGE_VAL;
   for (int it = 0; it < steps; ++it) {
     HIPCHK(hipMemsetAsync(h->ref_nrm.p, 0, 2 * sizeof(double), st));
-    HIPCHK(launch_residual(st, n, h->Arowptr.p, h->Arow_ent.p, h->Acol.p, h->A.p, dx, h->ref_b.p, h->ref_r.p,
-                           h->ref_nrm.p));
+    HIPCHK(residual(dx, h->ref_b.p, h->ref_r.p, h->ref_nrm.p));
     long long rec[16];
     rc = read_status(h, nullptr, 0, reinterpret_cast<const int32_t*>(h->ref_nrm.p), 4, rec);
     if (rc != SMLU_OK) return rc;
@@ -272,7 +292,7 @@ static int solve_refined(smlu_handle* h, const double* db, double* dx) {
     h->refine_berr = berr;
     if (berr <= eps || berr > 0.5 * prev) break;
     prev = berr;
-    rc = run_solve_dev(h, h->ref_r.p, h->ref_d.p, 0);
+    rc = solve(h->ref_r.p, h->ref_d.p);
     if (rc != SMLU_OK) return rc;
     HIPCHK(launch_axpy1(st, n, h->ref_d.p, dx));
     ++h->refine_steps;
@@ -280,6 +300,14 @@ static int solve_refined(smlu_handle* h, const double* db, double* dx) {
   HIPCHK(hipStreamSynchronize(st));
   h->solve_ms = ms;   // the plain solve's time (refinement steps reported separately)
   return SMLU_OK;
+}
+
+static int solve_refined(smlu_handle* h, const double* db, double* dx) {
+  return solve_refined_by(
+      h, db, dx, [&](const double* b, double* x) { return run_solve_dev(h, b, x, 0); },
+      [&](const double* x, const double* b, double* r, double* nrm) {
+        return launch_residual(h->stream, h->plan.n, h->Arowptr.p, h->Arow_ent.p, h->Acol.p, h->A.p, x, b, r, nrm);
+      });
 }
 
 int smlu_residual_device(smlu_handle* h, const double* d_x, const double* d_b, double* d_r, double* nrm) {
@@ -454,67 +482,16 @@ static int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* d
     rh.n = nrhs;
   }
   HIPCHK(launch_perm_in_t(st, P.n, h->q.p, db, ldb, w, conj, rh));
-  // a level's side launches on the side stream, forked after everything before the level and joined
-  // before the next level -- and on the error path, so a failed launch never leaves the side stream
-  // unjoined (inside a capture that would invalidate it)
-  auto run_seq = [&](const std::vector<Launch>& seq) {
-    bool forked = false;
-    hipError_t e = hipSuccess;
-    for (size_t i = 0; i < seq.size() && e == hipSuccess; ++i) {
-      const Launch& L = seq[i];
-      const bool first = L.grp > 0 && (i == 0 || seq[i - 1].grp != L.grp);
-      const bool last = L.grp > 0 && (i + 1 == seq.size() || seq[i + 1].grp != L.grp);
-      if (first) {
-        e = hipEventRecord(h->fork_ev, st);
-        if (e == hipSuccess) e = hipStreamWaitEvent(h->side, h->fork_ev, 0);
-        forked = e == hipSuccess;
-      }
-      if (e == hipSuccess) e = run_solve_launch_t(h, L, w, v, rh, L.side && forked ? h->side : st);
-      if (e == hipSuccess && last && forked) {
-        e = hipEventRecord(h->join_ev, h->side);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, h->join_ev, 0);
-        if (e == hipSuccess) forked = false;
-      }
-    }
-    if (forked) {
-      (void)hipEventRecord(h->join_ev, h->side);
-      (void)hipStreamWaitEvent(st, h->join_ev, 0);
-    }
+  auto launch = [&](const Launch& L, hipStream_t s) { return run_solve_launch_t(h, L, w, v, rh, s); };
+  auto passes = [&]() {   // the whole of fwdm, then of bwdm, with the side-stream overlap
+    hipError_t e = walk_launches(h, h->sch.fwdm, 0, h->sch.fwdm.size(), true, launch);
+    if (e == hipSuccess) e = walk_launches(h, h->sch.bwdm, 0, h->sch.bwdm.size(), true, launch);
     if (e != hipSuccess) return fail(h, SMLU_ERR_HIP, std::string("HIP error: ") + hipGetErrorString(e) + " in the transposed solve");
     return (int)SMLU_OK;
   };
-  auto passes = [&]() {
-    int rc = run_seq(h->sch.fwdm);
-    return rc != SMLU_OK ? rc : run_seq(h->sch.bwdm);
-  };
-  // the two passes (fixed pointers: the handle's wrk / vbuf, or wrkm / vbufm) captured once per batch
-  // width into a hipGraph and replayed
-  const int key = kTransGraphKey + rh.n;
-  hipGraphExec_t ex = nullptr;
-  if (!tune().no_graph && !h->graph_failed) {
-    for (auto& g : h->sol_execs)
-      if (g.first == key) ex = g.second;
-    if (!ex) {
-      hipGraph_t g = nullptr;
-      HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-      int rc = passes();
-      hipError_t ec = hipStreamEndCapture(st, &g);
-      if (rc == SMLU_OK && ec == hipSuccess && g) ec = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-      if (g) (void)hipGraphDestroy(g);
-      if (rc != SMLU_OK || ec != hipSuccess || !ex) {
-        (void)hipGetLastError();
-        h->graph_failed = true;
-        ex = nullptr;
-      } else {
-        h->sol_execs.push_back({key, ex});
-      }
-    }
-  }
-  if (ex) HIPCHK(hipGraphLaunch(ex, st));
-  else {
-    int rc = passes();
-    if (rc != SMLU_OK) return rc;
-  }
+  // the two passes (fixed pointers: the handle's wrk / vbuf, or wrkm / vbufm), one graph per batch width
+  int rc = run_graphed(h, !tune().no_graph, kTransGraphKey + rh.n, passes);
+  if (rc != SMLU_OK) return rc;
   ++h->trans_passes;
   HIPCHK(launch_perm_out_t(st, P.n, h->p0.p, h->Rs.p, w, dx, ldx, conj, rh));
   HIPCHK(tm.end(stop));
@@ -527,44 +504,14 @@ static int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* d
 // The transposed solve with solve_refined's refinement rule: r = b - A^T x by columns of A's CSC,
 // componentwise denominator |A^T||x| + |b|, same stop test and the same refine_* stats.
 static int solve_refined_t(smlu_handle* h, int conj, const double* db, double* dx) {
-  const int steps = auto_refine_steps(h);
-  h->refine_steps = 0;
-  h->refine_resid = -1;
-  h->refine_berr = -1;
-  if (steps == 0) return run_solve_t_dev(h, conj, db, dx);
   Plan& P = h->plan;
-  const int64_t n = P.n;
-  hipStream_t st = h->stream;
-  int rc0 = ensure_residual(h);
-  if (rc0 != SMLU_OK) return rc0;
-  if (!h->Acolp.p) HIPCHK(h->Acolp.upload(P.Acolptr.data(), P.Acolptr.size(), st));
-  HIPCHK(hipMemcpyAsync(h->ref_b.p, db, sizeof(double) * n, hipMemcpyDeviceToDevice, st));   // db may alias dx
-  int rc = run_solve_t_dev(h, conj, h->ref_b.p, dx);
-  if (rc != SMLU_OK) return rc;
-  const double ms = h->solve_ms;
-  const double eps = std::ldexp(1.0, -51);   // 4 unit roundoffs
-  double prev = HUGE_VAL;
-  for (int it = 0; it < steps; ++it) {
-    HIPCHK(hipMemsetAsync(h->ref_nrm.p, 0, 2 * sizeof(double), st));
-    HIPCHK(launch_residual_t(st, n, h->Acolp.p, h->Arow.p, h->A.p, dx, h->ref_b.p, h->ref_r.p, h->ref_nrm.p, conj));
-    long long rec[16];
-    rc = read_status(h, nullptr, 0, reinterpret_cast<const int32_t*>(h->ref_nrm.p), 4, rec);
-    if (rc != SMLU_OK) return rc;
-    double nrm, berr;
-    std::memcpy(&nrm, &rec[6], sizeof nrm);
-    std::memcpy(&berr, &rec[7], sizeof berr);
-    h->refine_resid = nrm;
-    h->refine_berr = berr;
-    if (berr <= eps || berr > 0.5 * prev) break;
-    prev = berr;
-    rc = run_solve_t_dev(h, conj, h->ref_r.p, h->ref_d.p);
-    if (rc != SMLU_OK) return rc;
-    HIPCHK(launch_axpy1(st, n, h->ref_d.p, dx));
-    ++h->refine_steps;
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  h->solve_ms = ms;   // the plain solve's time (refinement steps reported separately)
-  return SMLU_OK;
+  if (auto_refine_steps(h) != 0 && !h->Acolp.p)
+    HIPCHK(h->Acolp.upload(P.Acolptr.data(), P.Acolptr.size(), h->stream));
+  return solve_refined_by(
+      h, db, dx, [&](const double* b, double* x) { return run_solve_t_dev(h, conj, b, x); },
+      [&](const double* x, const double* b, double* r, double* nrm) {
+        return launch_residual_t(h->stream, P.n, h->Acolp.p, h->Arow.p, h->A.p, x, b, r, nrm, conj);
+      });
 }
 
 // op and handle checks shared by the four entry points; *conj: conjugate in and out

@@ -41,7 +41,18 @@ def main():
         F.solve_device(x1, B[0].contiguous())
         torch.cuda.synchronize()
         hs = hashlib.sha1(X.cpu().numpy().tobytes() + x1.cpu().numpy().tobytes()).hexdigest()[:16]
-        print(name, h.hexdigest()[:16], "solves", hs, "repivots", F.stat("repivots"))
+        # transposed solves: one column, and batches of 8 and 16 (the batch widths 1, 8, 16)
+        ht = []
+        B16 = torch.from_numpy(np.random.default_rng(13).standard_normal((16, n))).cuda()
+        for k in (1, 8, 16):
+            Xt = torch.empty_like(B16[:k])
+            if k == 1:
+                F.solve_device(Xt[0], B16[0].contiguous(), trans="T")
+            else:
+                F.solve_multi_device(Xt, B16[:k].contiguous(), trans="T")
+            torch.cuda.synchronize()
+            ht.append(hashlib.sha1(Xt.cpu().numpy().tobytes()).hexdigest()[:16])
+        print(name, h.hexdigest()[:16], "solves", hs, "trans_1_8_16", *ht, "repivots", F.stat("repivots"))
         F.close()
 
 
