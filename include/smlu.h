@@ -177,6 +177,43 @@ int smlu_solve_trans_multi(smlu_handle* h, int op, int64_t nrhs, const double* B
 int smlu_solve_trans_multi_device(smlu_handle* h, int op, int64_t nrhs, const double* d_B, int64_t ldb,
                                   double* d_X, int64_t ldx);
 
+/* logabsdet(F) / det(F) (Julia's LinearAlgebra on an lu object; umfpack_get_determinant; not in the
+ * reference): log|det A| of the current factorization and its sign, from the factors on the device
+ * -- the diagonal of U, Rs and the parities of the row and column orders and of every front's pivot
+ * permutation -- with no factor export: a few words come back in one small copy.  *sign = +1 or -1.
+ * Deterministic: two evaluations of one factorization are bitwise equal.  The result is cached per
+ * factorization (smlu_stat "logabsdet_evals" counts the device evaluations so far), and every
+ * refactor invalidates it.  SMLU_ERR_ARG: NULL handle or output.  SMLU_ERR_STATE: no numeric
+ * factorization (none yet, or a singular one), a partitioned handle (smlu_dist_*), or a ComplexF64
+ * handle (smlu_logabsdet_z). */
+int smlu_logabsdet(smlu_handle* h, double* logabs, double* sign);
+
+/* The same for a ComplexF64 handle: log|det A| and the phase det A / |det A| as (re, im), modulus 1.
+ * Folded from the real-equivalent factors like smlu_get_factors_z (complex pivots
+ * U_K[2k, 2k] - i U_K[2k, 2k+1], a factor i per row pair exchanged inside itself, the orders read
+ * as permutations of pairs), so it needs pair-preserving pivots: SMLU_ERR_STATE when a
+ * zero-free-diagonal row transversal was needed, as there, and on a real handle. */
+int smlu_logabsdet_z(smlu_handle* h, double* logabs, double phase[2]);
+
+/* Reciprocal condition estimate 1 / (||A|| * est||A^-1||) of the current factorization in the 1-norm
+ * or the infinity norm (UMFPACK_RCOND, SuperLU dgscon, LAPACK dgecon / zgecon; Julia's cond(A, 1) is
+ * its inverse; not in the reference).  ||A|| is exact, from the handle's device copy of the values
+ * (complex handle: sums of complex moduli); est||A^-1|| is the Hager / Higham estimate as LAPACK's
+ * dlacn2 / zlacn2 run it (at most 5 iterations, at most 11 solves with A and A^H), a lower bound of
+ * the true norm.  It is a property of the factors: the solves are the plain factor solves, never
+ * refined, whatever smlu_opts.refine says; each transposed one counts in "solve_trans_passes".  The
+ * vectors stay on the device (the handle's own buffers, nothing is ordered on the caller's stream);
+ * the host reads one 64-byte record per reduction.  Deterministic (bitwise) and cached per
+ * factorization and norm.  *anorm / *ainvnorm (either may be NULL) receive the two factors;
+ * *rcond = 1 / (anorm * ainvnorm), or 0 when either is 0.  smlu_stat: "rcond_solves" (solves run by
+ * the last call, 0 for a cached answer; "rcond_solves_fwd" / "rcond_solves_adj" split them by
+ * direction), "rcond_iters".  SMLU_ERR_ARG: NULL handle or rcond, unknown norm.  SMLU_ERR_STATE: no
+ * numeric factorization (none yet, or a singular one), or a partitioned handle (transposed solves
+ * are single-GPU). */
+#define SMLU_NORM_ONE 1
+#define SMLU_NORM_INF 2
+int smlu_rcond(smlu_handle* h, int norm, double* rcond, double* anorm, double* ainvnorm);
+
 /* ParallelSparseLU(A::SparseMatrixCSC{Float64,Int32}) — Int32 index arrays;
  * converted to the Int64 path on the host. */
 int smlu_create_i32(int64_t n, const int32_t* colptr, const int32_t* rowval, const double* nzval,
@@ -273,7 +310,9 @@ int64_t     smlu_last_error_col(const smlu_handle* h);      /* column of a zero/
  * "n","nnzA","nsuper","nlevels","nnzL","nnzU","nnzLU","flops","upd","front_max","ns_max",
  * "factor_bytes","scratch_bytes","launches","analysis_ms","refactor_ms_last","solve_ms_last",
  * "growth_max","dense_flops","gemm_flops","ms_gemm","ms_panel","ms_trsm","ms_assemble",
- * "ms_small","ms_solve","solve_trans_passes". Returns NaN for an unknown key. */
+ * "ms_small","ms_solve","solve_trans_passes","rcond_solves","rcond_solves_fwd","rcond_solves_adj",
+ * "rcond_iters","logabsdet_evals".
+ * Returns NaN for an unknown key. */
 double smlu_stat(const smlu_handle* h, const char* key);
 
 /* ---- host-only symbolic analysis (no GPU needed; used by the CPU test suite) ------- */

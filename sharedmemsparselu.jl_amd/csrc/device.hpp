@@ -124,6 +124,10 @@ struct Rhs {
   int64_t ldx, ldv;
 };
 constexpr int kMultiRhs = 16;   // right-hand sides per solve launch
+// kernels_diag.hip: workgroups per reduction (one per CU of the MI355X) and the 64-bit words of
+// one workgroup's partial result
+constexpr int kDgMaxBlocks = 256;
+constexpr int kDgPartWords = 8;
 #ifndef SMLU_SWEEP_WK
 #define SMLU_SWEEP_WK 4
 #endif

@@ -4,7 +4,7 @@
 //   schedule.cpp  (device set-up, schedule upload)         factor.cpp  (refactorization)
 //   solve.cpp     (solves, refinement, chunked layout)     export.cpp  (factor export, pattern hand-over)
 //   complex.cpp   (ComplexF64 handles)                     dist.cpp    (RCCL, partitioned handles)
-//   smlu.cpp      (create / destroy / stats / plan API)
+//   smlu.cpp      (create / destroy / stats / plan API)    diag.cpp    (determinant, condition estimate)
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -107,6 +107,14 @@ hipError_t launch_perm_out_t(hipStream_t, int64_t, const int64_t*, const double*
                              int, Rhs);
 hipError_t launch_residual_t(hipStream_t, int64_t, const int64_t*, const int32_t*, const double*, const double*,
                              const double*, double*, double*, int);
+// kernels_diag.hip: determinant and condition estimate (each reduction ends in the 64-byte record rec)
+hipError_t launch_dg_logdet(hipStream_t, bool, int64_t, const int32_t*, const SNode*, const double*, const double*,
+                            const int32_t*, void*, long long*, long long);
+hipError_t launch_dg_norm(hipStream_t, bool, bool, int64_t, const int64_t*, const int32_t*, const int32_t*,
+                          const double*, void*, long long*, long long);
+hipError_t launch_dg_vec(hipStream_t, bool, int64_t, int, int64_t, double*);
+hipError_t launch_dg_sign(hipStream_t, bool, int64_t, const double*, double*, int, void*, long long*, long long);
+hipError_t launch_dg_argmax(hipStream_t, bool, int64_t, const double*, int64_t, void*, long long*, long long);
 }  // namespace smlu
 
 using namespace smlu;
@@ -284,6 +292,16 @@ struct smlu_handle {
   std::vector<int64_t> zcolptr, zrowval;   // complex pattern (0-based), for pattern checks
   DBuf<int64_t> d_zdst;
   DBuf<int32_t> d_zoff;
+  // determinant and condition estimate (diag.cpp): buffers allocated on first use; results cached
+  // per factorization (the nfactor they were computed for; index 0: 1-norm, 1: inf-norm)
+  DBuf<int32_t> dg_col2s;            // front of each column
+  DBuf<double> dg_x, dg_y, dg_xi;    // the estimator's vectors
+  DBuf<long long> dg_part, dg_rec;   // reduction partials; the record the host reads
+  long long dg_seq = 0;
+  int64_t det_version = -1, rc_version[2] = {-1, -1};
+  double det_logabs = 0, det_phase[2] = {1, 0};
+  double rc_anorm[2] = {0, 0}, rc_ainv[2] = {0, 0};
+  int64_t logabsdet_evals = 0, rcond_iters = 0, rcond_solves = 0, rcond_solves_fwd = 0, rcond_solves_adj = 0;
   ~smlu_handle() { release_all(); }
   void release_buffers() {
     if (stream) (void)hipSetDevice(device);
@@ -304,6 +322,12 @@ struct smlu_handle {
     sn.free();
     d_zdst.free();
     d_zoff.free();
+    dg_col2s.free();
+    dg_x.free();
+    dg_y.free();
+    dg_xi.free();
+    dg_part.free();
+    dg_rec.free();
     xtasks.free();
     aents.free();
     ftiles.free();
@@ -481,6 +505,13 @@ int refactor_csc_impl(smlu_handle* h, int64_t n, const int64_t* colptr, const in
                       const double* nzval, const std::vector<int64_t>* preorder);
 int exec_comm(smlu_handle* h, int id);                   // dist.cpp
 int ensure_residual(smlu_handle* h);                     // solve.cpp
+int ensure_acol(smlu_handle* h);
+// the plain (never refined) factor solves on device vectors: mode 0 ldiv, 1 lsolve, 2 rsolve; and the
+// transposed pass pair (a ComplexF64 handle: A^H; conj: the plain transpose)
+int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode, int nrhs = 1, int64_t ldb = 0,
+                  int64_t ldx = 0);
+int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* dx, int nrhs = 1, int64_t ldb = 0,
+                    int64_t ldx = 0);
 
 
 struct Exported {

@@ -791,6 +791,26 @@ std::string Plan::build(int64_t n_, const int64_t* colptr, const int64_t* rowval
     for (int64_t c = 0; c < n; ++c)
       for (int64_t e = Acolptr[c]; e < Acolptr[c + 1]; ++e) Arow_ent[pos[Arow[e]]++] = (int32_t)e;
   }
+  // parities of the row pre-order and the column order (the determinant's sign), by cycle counting;
+  // pair_parity: the same for the orders read as permutations of index pairs (2k, 2k+1), which is
+  // what a ComplexF64 handle's real-equivalent orders are, -1 when they do not keep the pairs
+  {
+    auto parity = [](const std::vector<int64_t>& v, int64_t m, int64_t step) {
+      std::vector<char> seen((size_t)m, 0);
+      int64_t cycles = 0;
+      for (int64_t i = 0; i < m; ++i) {
+        if (seen[i]) continue;
+        ++cycles;
+        for (int64_t j = i; !seen[j]; j = v[step * j] / step) seen[j] = 1;
+      }
+      return (int)((m - cycles) & 1);
+    };
+    perm_parity = parity(p0, n, 1) ^ parity(q, n, 1);
+    bool pairs = n % 2 == 0;
+    for (int64_t k = 0; pairs && k < n; k += 2)
+      pairs = p0[k] % 2 == 0 && p0[k + 1] == p0[k] + 1 && q[k] % 2 == 0 && q[k + 1] == q[k] + 1;
+    pair_parity = pairs ? parity(p0, n / 2, 2) ^ parity(q, n / 2, 2) : -1;
+  }
   phase(9);
   analysis_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return "";

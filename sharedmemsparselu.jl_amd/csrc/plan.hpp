@@ -78,6 +78,8 @@ struct Plan {
   std::vector<int64_t> p0, p0inv; // rows (== q unless given)
   bool given_order = false;
   bool matched = false;           // rows pre-permuted by a zero-free-diagonal transversal
+  int perm_parity = 0;            // parity of p0 times parity of q (0 even, 1 odd): the determinant's sign
+  int pair_parity = -1;           // ... of p0 and q as permutations of the pairs (2k, 2k+1); -1: pairs not kept
 
   // ---- exact (pre-relaxation) supernodes: structure of L column j in t=col2t[j] is
   //      {j..last(t)} U R_t  (R_t sorted, all > last(t)) ----

@@ -242,6 +242,13 @@ double smlu_stat(const smlu_handle* h, const char* key) {
   if (k == "solve_trans_passes") {   // transposed pass pairs (U^T then L^T) run so far, one per batch of columns
     return (double)h->trans_passes;
   }
+  // determinant and condition estimate (diag.cpp): solves and iterations of the last smlu_rcond (a
+  // cached answer runs none), split into forward and adjoint passes; device evaluations of the determinant
+  if (k == "rcond_solves") return (double)h->rcond_solves;
+  if (k == "rcond_solves_fwd") return (double)h->rcond_solves_fwd;
+  if (k == "rcond_solves_adj") return (double)h->rcond_solves_adj;
+  if (k == "rcond_iters") return (double)h->rcond_iters;
+  if (k == "logabsdet_evals") return (double)h->logabsdet_evals;
   if (k == "sweep_status") {     // the device flag itself (cleared whenever a solve reports it)
     int32_t v = 0;
     if (h->sstatus.p && hipMemcpy(&v, h->sstatus.p, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;

@@ -109,8 +109,7 @@ static int run_graphed(smlu_handle* h, bool use_graph, int key, F&& body) {
   return SMLU_OK;
 }
 
-static int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode, int nrhs = 1, int64_t ldb = 0,
-                         int64_t ldx = 0) {
+int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode, int nrhs, int64_t ldb, int64_t ldx) {
   // mode 0: ldiv (b -> x); 1: lsolve in place on dx (final order); 2: rsolve in place.
   // nrhs > 1 (mode 0, one GPU): columns of db / dx with leading dimensions ldb / ldx.
   Plan& P = h->plan;
@@ -238,18 +237,23 @@ static int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode,
 int ensure_residual(smlu_handle* h) {
   Plan& P = h->plan;
   const int64_t n = P.n;
-  hipStream_t st = h->stream;
   if (!h->ref_b.p) {
     HIPCHK(h->ref_b.alloc((size_t)n));
     HIPCHK(h->ref_r.alloc((size_t)n));
     HIPCHK(h->ref_d.alloc((size_t)n));
     HIPCHK(h->ref_nrm.alloc(2));
   }
+  return ensure_acol(h);
+}
+
+// The column of every A entry (residuals, dominance check, row sums of a complex handle).
+int ensure_acol(smlu_handle* h) {
+  Plan& P = h->plan;
   if (!h->Acol.p) {
     std::vector<int32_t> ac((size_t)std::max<int64_t>(P.nnzA, 1));
-    for (int64_t c = 0; c < n; ++c)
+    for (int64_t c = 0; c < P.n; ++c)
       for (int64_t e = P.Acolptr[c]; e < P.Acolptr[c + 1]; ++e) ac[e] = (int32_t)c;
-    HIPCHK(h->Acol.upload(ac.data(), ac.size(), st));
+    HIPCHK(h->Acol.upload(ac.data(), ac.size(), h->stream));
   }
   return SMLU_OK;
 }
@@ -462,8 +466,7 @@ constexpr int kTransGraphKey = 1 << 12;
 // unused).  A batch runs in wrkm / vbufm, the forward batch's buffers (calls on one handle are
 // serialised); db may alias dx when ldb == ldx: the whole batch is permuted into the work buffer
 // before any x is written.
-static int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* dx, int nrhs = 1, int64_t ldb = 0,
-                           int64_t ldx = 0) {
+int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* dx, int nrhs, int64_t ldb, int64_t ldx) {
   Plan& P = h->plan;
   if (nrhs < 1 || nrhs > kMultiRhs) return fail(h, SMLU_ERR_STATE, "transposed batch: 1 to 16 right-hand sides");
   hipStream_t st = h->stream;

@@ -186,6 +186,42 @@ end
 ldiv!(x::AbstractVecOrMat, W::TransposedLU, b::AbstractVecOrMat) = _ldiv_trans!(Int32(1), x, W.parent, b)
 ldiv!(x::AbstractVecOrMat, W::AdjointLU, b::AbstractVecOrMat) = _ldiv_trans!(Int32(2), x, W.parent, b)
 
+# logabsdet(F), logdet(F), det(F) and cond(F, p) from the factors on the GPU (smlu_logabsdet*,
+# smlu_rcond): no factor download.  The sign of a ComplexF64 factorization is its phase.
+function LinearAlgebra.logabsdet(F::ParallelSparseLU{Tf}) where {Tf}
+    la = Ref{Float64}(0.0)
+    if Tf === ComplexF64
+        ph = zeros(Float64, 2)
+        check(ccall((:smlu_logabsdet_z, libsmlu), Int32, (Ptr{Cvoid}, Ref{Float64}, Ptr{Float64}),
+                    F.handle, la, ph), F.handle)
+        return la[], complex(ph[1], ph[2])
+    end
+    sg = Ref{Float64}(0.0)
+    check(ccall((:smlu_logabsdet, libsmlu), Int32, (Ptr{Cvoid}, Ref{Float64}, Ref{Float64}),
+                F.handle, la, sg), F.handle)
+    return la[], sg[]
+end
+function LinearAlgebra.logdet(F::ParallelSparseLU{Tf}) where {Tf}
+    la, sg = logabsdet(F)
+    Tf === ComplexF64 && return complex(la, angle(sg))
+    sg < 0 && throw(DomainError(sg, "determinant is negative: use logabsdet"))
+    return la
+end
+function LinearAlgebra.det(F::ParallelSparseLU)
+    la, sg = logabsdet(F)
+    return sg * exp(la)
+end
+# cond(F, 1) / cond(F, Inf): ||A|| est||A^-1|| (LAPACK's dgecon / zgecon estimator); SMLU_NORM_ONE = 1,
+# SMLU_NORM_INF = 2 (include/smlu.h).  No default p: LinearAlgebra's cond(A) is the 2-norm, which the
+# factors do not give.
+function LinearAlgebra.cond(F::ParallelSparseLU, p::Real)
+    p == 1 || p == Inf || throw(ArgumentError("cond(F, p): p must be 1 or Inf, got $p"))
+    r = Ref{Float64}(0.0)
+    check(ccall((:smlu_rcond, libsmlu), Int32, (Ptr{Cvoid}, Int32, Ref{Float64}, Ptr{Float64}, Ptr{Float64}),
+                F.handle, Int32(p == 1 ? 1 : 2), r, C_NULL, C_NULL), F.handle)
+    return r[] == 0 ? Inf : inv(r[])
+end
+
 function _trisolve!(upper::Bool, F::ParallelSparseLU{Tf}, x::AbstractVector) where {Tf}
     xx = x isa Vector{Tf} ? x : Vector{Tf}(x)
     check(ccall(fnptr(upper ? :smlu_rsolve : :smlu_lsolve), Int32, (Ptr{Cvoid}, Ptr{Tf}), F.handle, xx),

@@ -35,6 +35,10 @@ SMLU_OP_N = 0
 SMLU_OP_T = 1
 SMLU_OP_H = 2
 
+# norm of smlu_rcond
+SMLU_NORM_ONE = 1
+SMLU_NORM_INF = 2
+
 ORDER_AUTO, ORDER_NATURAL, ORDER_GEOMETRIC_ND, ORDER_GRAPH_ND, ORDER_GIVEN, ORDER_AMD = range(6)
 
 
@@ -81,6 +85,9 @@ SIGNATURES = {
     "smlu_solve_trans_device": (i32, [vp, i32, vp, vp]),
     "smlu_solve_trans_multi": (i32, [vp, i32, i64, vp, i64, vp, i64]),
     "smlu_solve_trans_multi_device": (i32, [vp, i32, i64, vp, i64, vp, i64]),
+    "smlu_logabsdet": (i32, [vp, f64p, f64p]),
+    "smlu_logabsdet_z": (i32, [vp, f64p, f64p]),
+    "smlu_rcond": (i32, [vp, i32, f64p, f64p, f64p]),
     "smlu_create_i32": (i32, [i64, vp, vp, vp, ctypes.POINTER(SmluOpts), ctypes.POINTER(vp)]),
     "smlu_create_z": (i32, [i64, vp, vp, vp, ctypes.POINTER(SmluOpts), ctypes.POINTER(vp)]),
     "smlu_refactor_z": (i32, [vp, vp]),

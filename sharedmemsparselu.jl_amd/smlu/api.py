@@ -8,6 +8,8 @@ ldiv!(x, F, b)                      ldiv_(x, F, b)                :286-342
 ldiv!(x, transpose(F), b)           ldiv_(x, F, b, trans="T")     (not in the reference)
 ldiv!(x, F', b)                     ldiv_(x, F, b, trans="C")     (not in the reference)
 lsolve!(F, x), rsolve!(F, x)        lsolve_(F, x), rsolve_(F, x)  :349-392
+logabsdet(F), det(F), logdet(F)     F.logabsdet() F.det() F.logdet()  (not in the reference)
+cond(F, 1), cond(F, Inf)            F.condest("1"|"inf"), F.rcond()   (not in the reference)
 F.L F.U F.p F.q F.Rs                F.L F.U F.p F.q F.Rs          :45-52 (0-based here)
 cleanup_ParallelSparseLU!(F)        cleanup_ParallelSparseLU_(F)  :31 (exported, undefined there)
 DimensionMismatch                   DimensionMismatch             :288-290
@@ -64,6 +66,14 @@ def _op(trans):
         return {"N": C.SMLU_OP_N, "T": C.SMLU_OP_T, "C": C.SMLU_OP_H}[trans]
     except (KeyError, TypeError):
         raise ValueError(f'trans must be "N", "T" or "C", got {trans!r}') from None
+
+
+def _norm(norm):
+    """norm = "1" | "inf" -> SMLU_NORM_ONE / SMLU_NORM_INF (include/smlu.h)."""
+    try:
+        return {"1": C.SMLU_NORM_ONE, "inf": C.SMLU_NORM_INF}[norm]
+    except (KeyError, TypeError):
+        raise ValueError(f'norm must be "1" or "inf", got {norm!r}') from None
 
 
 def _check(rc, h=None):
@@ -315,6 +325,50 @@ class ParallelSparseLU:
                     self._h)
             return _check(C.lib().smlu_solve_multi_device(self._h, nrhs, ctypes.c_void_p(d_B.data_ptr()), ld,
                                                           ctypes.c_void_p(d_X.data_ptr()), ld), self._h)
+
+    # ---- determinant and condition estimate (smlu_logabsdet*, smlu_rcond) ----
+    def logabsdet(self):
+        """(log|det A|, sign) of the current factorization, as Julia's logabsdet(F): sign is +1.0 or
+        -1.0, and a complex number of modulus 1 on a complex factorization.  Computed on the device
+        from the factors' diagonal and permutations; cached until the next refactor."""
+        la = ctypes.c_double()
+        if self.is_complex:
+            ph = (ctypes.c_double * 2)()
+            _check(C.lib().smlu_logabsdet_z(self._h, ctypes.byref(la), ph), self._h)
+            return la.value, complex(ph[0], ph[1])
+        sg = ctypes.c_double()
+        _check(C.lib().smlu_logabsdet(self._h, ctypes.byref(la), ctypes.byref(sg)), self._h)
+        return la.value, sg.value
+
+    def det(self):
+        """det(F) = sign * exp(log|det A|); overflows to inf where the determinant does."""
+        la, sg = self.logabsdet()
+        return sg * np.exp(la)
+
+    def logdet(self):
+        """logdet(F): log(det A).  A negative real determinant raises, as Julia's DomainError does;
+        a complex factorization returns log|det A| + i arg(det A)."""
+        la, sg = self.logabsdet()
+        if self.is_complex:
+            return complex(la, np.angle(sg))
+        if sg < 0:
+            raise ValueError("logdet: the determinant is negative (use logabsdet)")
+        return la
+
+    def rcond(self, norm="1", parts=False):
+        """Reciprocal condition estimate 1 / (||A|| est||A^-1||) in the 1-norm (norm="1") or the
+        infinity norm (norm="inf") from the current factors (smlu_rcond: LAPACK's dgecon / zgecon
+        estimator on the GPU solves).  parts=True returns (rcond, ||A||, est||A^-1||)."""
+        nm = _norm(norm)
+        r, an, ai = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        _check(C.lib().smlu_rcond(self._h, nm, ctypes.byref(r), ctypes.byref(an), ctypes.byref(ai)), self._h)
+        return (r.value, an.value, ai.value) if parts else r.value
+
+    def condest(self, norm="1"):
+        """Estimate of cond(A) in the given norm: ||A|| est||A^-1|| (inf when rcond is 0)."""
+        _norm(norm)
+        _, an, ai = ParallelSparseLU.rcond(self, norm, parts=True)
+        return an * ai if an * ai > 0 else float("inf")
 
     def close(self):
         h = getattr(self, "_h", None)

@@ -18,6 +18,15 @@ the per-block sequences; prints both times, the ratio and the number of transpos
 call took (K on a library that solves column by column, ceil(K / 16) with the batched kernels).
 
     python tools/solve_timing.py --trans --nrhs 8 [--side 128] [--reps 5]
+
+--rcond: the condition estimate (smlu_rcond) beside the forward and transposed solves of the same
+handle (the default schedule: forward on the sync-free sweeps), same protocol: warm-up, then
+alternating blocks of --reps calls each, median over all of them.  Every timed estimate follows a
+refactor of the same values (untimed), since the result is cached per factorization.  The yardstick
+is the estimate's own solve counts times the two solve times; what is left is the estimator's
+overhead (its elementwise kernels and record readbacks).  Also times smlu_logabsdet.
+
+    python tools/solve_timing.py --rcond [--side 128] [--reps 5] [--norm 1]
 """
 import argparse
 import os
@@ -35,6 +44,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--trans", action="store_true")
     ap.add_argument("--nrhs", type=int, default=1, help="with --trans: columns per solve")
+    ap.add_argument("--rcond", action="store_true")
+    ap.add_argument("--norm", default="1", help='with --rcond: "1" or "inf"')
     args = ap.parse_args()
     if args.trans:
         os.environ["SMLU_SOLVE_STEPS"] = "1"   # read when the handle's schedule is built
@@ -61,6 +72,48 @@ def main():
 
     b = torch.from_numpy(rng.random(n)).to(dev)
     x = torch.empty_like(b)
+    if args.rcond:
+        xt = torch.empty_like(b)
+        vals = torch.from_numpy(np.ascontiguousarray(A.data)).to(dev)
+
+        def clock(fn):
+            t0 = time.perf_counter()
+            r = fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3, r
+
+        fwd = lambda: F.solve_device(x, b)
+        trn = lambda: F.solve_device(xt, b, trans="T")
+        est = lambda: F.rcond(args.norm, parts=True)
+        for fn in (fwd, trn, est, F.logabsdet):   # warm-up: code objects, buffers, the captured graphs
+            fn()
+        torch.cuda.synchronize()
+        ts = {"fwd": [], "trans": [], "rcond": [], "logabsdet": []}
+        res = set()
+        for _ in range(3):      # alternating blocks
+            for key, fn in (("fwd", fwd), ("trans", trn)):
+                for _ in range(args.reps):
+                    ts[key].append(clock(fn)[0])
+            for _ in range(args.reps):
+                F.refactor_device(vals)
+                torch.cuda.synchronize()
+                t, r = clock(est)
+                ts["rcond"].append(t)
+                res.add(r)
+                ts["logabsdet"].append(clock(F.logabsdet)[0])
+        assert len(res) == 1, res   # the same values: bitwise the same estimate
+        for key, v in ts.items():
+            out[f"ms_{key}"] = float(np.median(v))
+            out[f"ms_{key}_min_max"] = (float(min(v)), float(max(v)))
+        out["norm"] = args.norm
+        out["rcond"], out["anorm"], out["ainvnorm"] = res.pop()
+        nf, na = F.stat("rcond_solves_fwd"), F.stat("rcond_solves_adj")
+        out["rcond_solves_fwd"], out["rcond_solves_adj"], out["rcond_iters"] = nf, na, F.stat("rcond_iters")
+        out["ms_yardstick"] = nf * out["ms_fwd"] + na * out["ms_trans"]
+        out["overhead_share"] = (out["ms_rcond"] - out["ms_yardstick"]) / out["ms_yardstick"]
+        out["logabsdet"] = F.logabsdet()
+        print(out, flush=True)
+        return
     if args.trans:
         assert F.stat("solve_sweeps") == 0
         xt = torch.empty_like(b)
