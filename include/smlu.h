@@ -441,6 +441,11 @@ int smlu_plan_schedule_digest(const smlu_plan* plan, int32_t nparts, int32_t ran
  *                      0 or negative: off.  smlu_stat: f22_gather_fronts, f22_gather_entries,
  *                      launches_mfma128_gather
  *   SMLU_F22_GATHER_CH=c  ... only fronts with at most c contributing children (default 8)
+ *   SMLU_LSIDE_MIN=r   diagonal-tile fronts with at least r rows below the current outer block
+ *                      (default 2048) solve and update those L rows on the handle's side stream,
+ *                      off the panel chain, and join them before the block's trailing update (one
+ *                      GPU, dominant values; bitwise the same factors); 0: off.  smlu_stat:
+ *                      side_launches, side_rows
  *   SMLU_SWEEP_SPIN=s  polls before a sync-free solve wait gives up and the solve is re-run on the
  *                      per-block schedule (default 2^22; 0 = at once, tests)
  *   SMLU_SOLVE_STEPS=1 per-block solve launches instead of the sync-free sweeps

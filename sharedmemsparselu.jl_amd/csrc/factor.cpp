@@ -74,8 +74,67 @@ launches:
   auto group = [&](size_t i) { return h->sch.fac[i].kind == K_FRONT_LDS ? h->sch.fac[i].aux2 : 0; };
   int gi = 0;   // index of the current launch inside its group
   hipEvent_t gstop = nullptr;
+  // The side launches of the blocked fronts' steps (Launch.side: the L rows below the outer block,
+  // schedule_build.cpp step_solves) go on the side stream.  A run of them starts after the
+  // main-stream launch right ahead of it (the step's TRSM: NU_t and the block's U rows t are done;
+  // lside_ev is recorded there) and follows the earlier runs by stream order; the main stream does
+  // not wait for them between steps.  It joins them ahead of the launches of fac_joins_side -- the
+  // block's trailing update, the level's F22 update, the next level -- and at the end of the
+  // segment, so the side stream is idle again when a small-front group forks.  The join ahead of
+  // the trailing update also keeps the next block's panels from overwriting a tile-inverse slot
+  // (reused per outer block) that the side stream still reads.
+  // The run [d0, d1) is issued behind the main-stream launch that follows it: in the captured graph
+  // the main stream's next kernel is then the first successor of the step's TRSM and the side run
+  // the second.  Issued in schedule order, the side run came first, the replay continued the
+  // TRSM's queue with it and moved the rest of the chain to another queue at every step: 128^3
+  // 427 -> 516 ms.
+  // (profile mode: the events of side launches are taken on the side stream, so "trsm" and "gemm"
+  // then count overlapped time)
+  bool lpending = false;
+  auto ljoin = [&]() -> hipError_t {
+    if (!lpending) return hipSuccess;
+    lpending = false;
+    hipError_t e = hipEventRecord(h->ljoin_ev, h->side);
+    return e != hipSuccess ? e : hipStreamWaitEvent(st, h->ljoin_ev, 0);
+  };
+  size_t d0 = 0, d1 = 0;
+  int side_step = 0;
+  auto flush_side = [&]() -> hipError_t {
+    if (d0 == d1) return hipSuccess;
+    hipError_t e = hipStreamWaitEvent(h->side, h->lside_ev, 0);
+    lpending = true;
+    for (size_t i = d0; i < d1 && e == hipSuccess; ++i) {
+      const Launch& Q = h->sch.fac[i];
+      side_step = Q.step;
+      hipEvent_t stop = nullptr;
+      e = tm.begin(Q.kind, &stop, h->side);
+      if (e == hipSuccess) e = run_launch(h, Q, diag_tol, piv_tol, h->side);
+      if (e == hipSuccess) e = tm.end(stop);
+      if (e == hipSuccess && dbg) e = hipStreamSynchronize(h->side);
+    }
+    d0 = d1 = 0;
+    return e;
+  };
+  auto side_fail = [&](hipError_t e) {   // joined on the error path too (a capture stays valid)
+    (void)ljoin();
+    return fail(h, SMLU_ERR_HIP, std::string("HIP error '") + hipGetErrorString(e) + "' in a side launch, step " +
+                                     std::to_string(side_step));
+  };
   for (size_t li = lo; li < hi; ++li) {
     const Launch& L = h->sch.fac[li];
+    if (L.side) {
+      if (d0 == d1) {
+        HIPCHK(hipEventRecord(h->lside_ev, st));
+        d0 = li;
+      }
+      d1 = li + 1;
+      continue;
+    }
+    if (fac_joins_side(L.kind)) {
+      hipError_t e = flush_side();
+      if (e == hipSuccess) e = ljoin();
+      if (e != hipSuccess) return side_fail(e);
+    }
     const int64_t g = group(li);
     const bool cont = g > 0 && li > lo && group(li - 1) == g;
     const bool more = g > 0 && li + 1 < hi && group(li + 1) == g;
@@ -98,6 +157,8 @@ launches:
         (void)hipEventRecord(h->join_ev, h->side);
         (void)hipStreamWaitEvent(st, h->join_ev, 0);
       }
+      (void)flush_side();
+      (void)ljoin();
       char buf[256];
       std::snprintf(buf, sizeof buf, "HIP error '%s' in launch kind=%d step=%d off=%lld cnt=%lld nwg=%lld aux=%lld aux2=%lld",
                     hipGetErrorString(e), L.kind, L.step, (long long)L.off, (long long)L.cnt,
@@ -105,6 +166,7 @@ launches:
       return fail(h, SMLU_ERR_HIP, buf);
     }
     if (!grouped) HIPCHK(tm.end(stop));
+    if (hipError_t es = flush_side(); es != hipSuccess) return side_fail(es);
     if (gi >= 1 && !more) {   // join: the main stream continues after both branches
       HIPCHK(hipEventRecord(h->join_ev, h->side));
       HIPCHK(hipStreamWaitEvent(st, h->join_ev, 0));
@@ -113,6 +175,8 @@ launches:
       gstop = nullptr;
     }
   }
+  if (hipError_t es = flush_side(); es != hipSuccess) return side_fail(es);
+  HIPCHK(ljoin());
   return SMLU_OK;
 }
 

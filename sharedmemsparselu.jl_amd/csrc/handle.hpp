@@ -190,6 +190,10 @@ struct smlu_handle {
   // streams (fork / join by events, captured into the same graph as parallel branches)
   hipStream_t side = nullptr;
   hipEvent_t fork_ev = nullptr, join_ev = nullptr;
+  // ... and, during the blocked fronts' chain, the step launches on the L rows below the outer
+  // block (Launch.side): started behind the step's TRSM (lside_ev), joined before the block's
+  // trailing update (ljoin_ev)
+  hipEvent_t lside_ev = nullptr, ljoin_ev = nullptr;
   std::string err;
   int64_t errcol = -1;
   bool have_numeric = false;
@@ -380,7 +384,9 @@ struct smlu_handle {
     if (ev_caller) (void)hipEventDestroy(ev_caller);
     if (fork_ev) (void)hipEventDestroy(fork_ev);
     if (join_ev) (void)hipEventDestroy(join_ev);
-    fork_ev = join_ev = nullptr;
+    if (lside_ev) (void)hipEventDestroy(lside_ev);
+    if (ljoin_ev) (void)hipEventDestroy(ljoin_ev);
+    fork_ev = join_ev = lside_ev = ljoin_ev = nullptr;
     if (side) (void)hipStreamDestroy(side);
     side = nullptr;
     if (stream) (void)hipStreamDestroy(stream);

@@ -26,6 +26,7 @@ struct Tune {
   int64_t fullpiv_ns = -1;    // SMLU_FULLPIV_NS: largest ns with full-candidate pivoting (-1 = default rule)
   int64_t f22_gather_nu = 512;  // SMLU_F22_GATHER_NU: fronts with nu >= this have their F22 assembled by the Schur GEMM (<= 0: off)
   int64_t f22_gather_ch = 8;    // SMLU_F22_GATHER_CH: ... if at most this many children contribute
+  int64_t lside_min = 2048;   // SMLU_LSIDE_MIN: GEMM-form fronts with at least this many rows below the outer block solve and update those L rows on the side stream (0: off)
   int sweep_spin = 1 << 22;  // SMLU_SWEEP_SPIN: polls before a sync-free solve wait gives up (0: at once)
   bool solve_steps = false;   // SMLU_SOLVE_STEPS=1: per-block solve launches instead of the sweeps
   bool no_graph = false;      // SMLU_NO_GRAPH: eager launches, no captured graphs

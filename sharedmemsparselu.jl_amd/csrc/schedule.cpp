@@ -199,6 +199,8 @@ int setup_device(smlu_handle* h) {
   if (!h->side) HIPCHK(hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, prio_hi));
   if (!h->fork_ev) HIPCHK(hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming));
   if (!h->join_ev) HIPCHK(hipEventCreateWithFlags(&h->join_ev, hipEventDisableTiming));
+  if (!h->lside_ev) HIPCHK(hipEventCreateWithFlags(&h->lside_ev, hipEventDisableTiming));
+  if (!h->ljoin_ev) HIPCHK(hipEventCreateWithFlags(&h->ljoin_ev, hipEventDisableTiming));
   hipStream_t st = h->stream;
   rank_layout_of(P, h->rank, h->nranks, h->lay);
   const Sizes z = sizes_of(P, h->lay, h->rank, h->nranks);

@@ -46,10 +46,18 @@ struct Launch {
   double flops = 0;
   // solves (one GPU): consecutive launches with the same grp > 0 are one level's fronts; in batched
   // solves (the per-block schedule) the side ones (small and tiny fronts) run on the handle's side
-  // stream next to the large fronts' chain
+  // stream next to the large fronts' chain.
+  // factorization (one GPU): side marks the K_TRSML / K_GEMM launches of a step that hold the L rows
+  // below the outer block (grp = level + 1); they run on the side stream, off the panel chain
   int grp = 0;
   bool side = false;
 };
+// Factor launches ahead of which the main stream waits for pending side launches: the readers of
+// the rows below an outer block (trailing and F22 updates) and whatever opens the next level.  The
+// end of the sequence joins too.  (The builder's checks and enqueue_factor share this rule.)
+inline bool fac_joins_side(int kind) {
+  return kind == K_GEMMO || kind == K_GEMM22 || kind == K_EXTADD || kind == K_FRONT_LDS;
+}
 
 // Host description of one copy of a pack / unpack step, resolved to device addresses once the
 // buffers exist: base 0 store, 1 scratch, 2 vbuf, 3 wrk (x), 4 send staging, 5 receive staging,
@@ -149,6 +157,9 @@ struct Schedule {
   std::vector<int32_t> g22inv;
   int64_t f22_gather_fronts = 0;
   double f22_gather_entries = 0;   // sum of nu^2 over those fronts
+  // L rows below the outer block on the side stream (Launch.side in fac): launches, and the rows
+  // their TRSM tasks take off the panel chain, summed over the steps
+  int64_t side_launches = 0, side_rows = 0;
   // statistics
   double gemm_flops = 0, gemm22_flops = 0;
   double gemm_bytes = 0;      // algorithmic bytes of the GEMM launches: A, B read, C read + written

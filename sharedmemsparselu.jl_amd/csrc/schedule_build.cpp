@@ -79,6 +79,8 @@ struct Builder {
   std::vector<int32_t> col_cnt, col_pos;           // front_columns' counters
   std::vector<std::vector<Launch>> bwd_levels;     // backward launches per level, emitted root first
   std::vector<char> f22g;                          // front -> its F22 is gathered by the Schur GEMM
+  int cur_level = 0;                               // the level whose launches are being emitted
+  std::vector<size_t> lvl_end;                     // S.fac.size() after each level (lside_check)
 
   Builder(const ScheduleInput& i, Schedule& s)
       : in(i), P(*i.plan), Y(*i.lay), S(s), rank(i.rank), nranks(i.nranks) {}
@@ -143,7 +145,7 @@ struct Builder {
   }
   // GEMM launches: 128x128 tiles when the launch has enough of them to fill the GPU,
   // otherwise 64x64 tiles (same per-element arithmetic, bitwise-identical results).
-  void add_gemm_launch(std::vector<GemmRec>& cand, double fl, int step, int kind = K_GEMM) {
+  void add_gemm_launch(std::vector<GemmRec>& cand, double fl, int step, int kind = K_GEMM, bool side = false) {
     if (cand.empty()) return;
     const bool count = kind != K_TRSML;   // GEMM-form TRSM is accounted as "trsm", not GEMM
     int64_t t128 = 0;
@@ -177,6 +179,13 @@ struct Builder {
     L.cnt = (int64_t)cand.size();
     L.nwg = tiles;
     L.flops = fl;
+    if (side) {   // the L rows below the outer block: the side stream (factor.cpp)
+      L.side = true;
+      L.grp = cur_level + 1;
+      ++S.side_launches;
+      if (kind == K_TRSML)
+        for (const GemmRec& g : cand) S.side_rows += g.m;
+    }
     S.fac.push_back(L);
     if (!count) return;
     S.gemm_flops += fl;
@@ -722,27 +731,127 @@ struct Builder {
     // GEMM-form step TRSM of the blocked fronts, in place:
     //   U rows [kb, kb+w) x columns [kb+w, oend):  C - (I - L_kk^-1) C = L_kk^-1 C
     //   L rows [kb+R, M) x columns [kb, kb+w):     C - C (I - U_kk^-1) = C U_kk^-1 (+ growth)
-    std::vector<GemmRec> tri, cand;
-    double fl = 0;
+    //
+    // L rows below the outer block on the side stream (lside): in a diagonal-tile step nothing
+    // before the block's trailing update (k = OB width) or the level's F22 update reads the rows
+    // [oend, M) of the block's columns -- the panels (k_panel_blk: R = w candidate rows, the tile's
+    // interchanges on rows [kb, kb+w)), k_laswp and k_urows stay inside rows [ostart, oend) -- so
+    // of a front with at least lside_min such rows both tasks are cut at row oend, and the lower
+    // parts form a second K_TRSML and a second K_GEMM launch marked `side`.  They need this step's
+    // panel (NU_t) and U rows, follow the previous step's side launches, and are joined ahead of
+    // the launches of fac_joins_side.  Same tiles, same k = 64 updates per element in the same order.
+    std::vector<GemmRec> tri, cand, stri, scand;
+    double fl = 0, sfl = 0;
     for (auto s : act) {
       const Step g = geom(s, t);
       const Operand F = kStore + S.hsn[s].Loff;
+      // rows of the L-row solve / the in-block update that stay in the chain
+      const int64_t cut = lside(s, g) ? g.oend : g.M;
       if (gform(s)) {
         if (g.oend - g.kb - g.w > 0) {
           const Operand X = F + (g.kb + g.w) * g.M + g.kb;
           tri.push_back(gemm_task(tinv_at(g.slot, false), X, X, g.w, g.oend - g.kb - g.w, g.w, 64, g.M, g.M));
+          tri.back().front = (int32_t)s;
         }
-        if (g.M - g.kb - g.R > 0) {
+        if (cut - g.kb - g.R > 0) {
           const Operand X = F + g.kb * g.M + g.kb + g.R;
-          tri.push_back(gemm_task(X, tinv_at(g.slot, true), X, g.M - g.kb - g.R, g.w, g.w, g.M, 64, g.M, (int32_t)s));
+          tri.push_back(gemm_task(X, tinv_at(g.slot, true), X, cut - g.kb - g.R, g.w, g.w, g.M, 64, g.M, (int32_t)s));
+          tri.back().front = (int32_t)s;
+        }
+        if (cut < g.M) {
+          const Operand X = F + g.kb * g.M + cut;
+          stri.push_back(gemm_task(X, tinv_at(g.slot, true), X, g.M - cut, g.w, g.w, g.M, 64, g.M, (int32_t)s));
+          stri.back().front = (int32_t)s;
         }
       }
       // inner trailing update: rows [kb+w, M) x columns [kb+w, oend) of the outer block
+      const size_t had = cand.size(), shad = scand.size();
       update(cand, fl, F + g.kb * g.M + g.kb + g.w, F + (g.kb + g.w) * g.M + g.kb,
-             F + (g.kb + g.w) * g.M + g.kb + g.w, g.M - g.kb - g.w, g.oend - g.kb - g.w, g.w, g.M, g.M, g.M);
+             F + (g.kb + g.w) * g.M + g.kb + g.w, cut - g.kb - g.w, g.oend - g.kb - g.w, g.w, g.M, g.M, g.M);
+      if (cut < g.M)
+        update(scand, sfl, F + g.kb * g.M + cut, F + (g.kb + g.w) * g.M + g.kb, F + (g.kb + g.w) * g.M + cut,
+               g.M - cut, g.oend - g.kb - g.w, g.w, g.M, g.M, g.M);
+      if (cand.size() > had) cand.back().front = (int32_t)s;
+      if (scand.size() > shad) scand.back().front = (int32_t)s;
     }
+    // (the side launches stand right behind the step's TRSM: factor.cpp records their start
+    // event after the last main-stream launch ahead of them, and issues them behind the next one)
     add_gemm_launch(tri, 0.0, (int)t, K_TRSML);
+    add_gemm_launch(stri, 0.0, (int)t, K_TRSML, true);
+    add_gemm_launch(scand, sfl, (int)t, K_GEMM, true);
     add_gemm_launch(cand, fl, (int)t);
+  }
+  // Whether step g of front s sends its L rows below the outer block to the side stream: one GPU,
+  // a schedule whose blocked fronts all pivot inside the diagonal tile (dominant values), and
+  // enough rows there to be worth two more launches per step (SMLU_LSIDE_MIN; 0: off)
+  bool lside(int64_t s, const Step& g) const {
+    return nranks == 1 && in.tn.lside_min > 0 && in.dominant && in.pivmode == 0 && !in.cpair && gform(s) &&
+           S.hsn[s].mode == 2 && g.M - g.oend >= in.tn.lside_min;
+  }
+  // The side launches checked over the finished factor sequence.  Every side task belongs to a
+  // diagonal-tile front, lies in the columns of one outer block, and its rows (C, and the L rows an
+  // update reads) start at or below that block's end and stay inside the front.  While a front has
+  // side launches pending, its step tasks on the main stream end at or above that row.  And a join
+  // (fac_joins_side, or the end of the sequence) comes before the first launch of another level.
+  // The join ahead of K_GEMMO is also what keeps the tile inverses alive: their slots are reused
+  // per outer block (slot = t mod OB/64, and per level by the next level's fronts), so the next
+  // block's panels must not start before the side stream has read NU of this block's steps.
+  void lside_check() {
+    if (S.side_launches == 0) return;
+    struct Pos {
+      int64_t row, col, oend, M;
+    };
+    auto where = [&](const GemmRec& g, const Operand& X, Pos& p) {
+      if (g.front < 0 || X.buf != kStore.buf) return false;
+      const SNode& r = S.hsn[g.front];
+      p.M = (int64_t)r.ns + r.nu;
+      const int64_t rel = X.off - r.Loff;
+      if (rel < 0 || rel >= p.M * r.ns) return false;
+      p.col = rel / p.M;
+      p.row = rel % p.M;
+      p.oend = std::min<int64_t>(r.ns, (p.col / S.ob + 1) * S.ob);
+      return true;
+    };
+    std::vector<char> pend(P.nsup, 0);   // fronts with side launches not yet joined
+    std::vector<int32_t> plist;
+    size_t lv = 0, plevel = 0;
+    for (size_t i = 0; i < S.fac.size(); ++i) {
+      while (lv < lvl_end.size() && lvl_end[lv] <= i) ++lv;   // the level of launch i
+      const Launch& L = S.fac[i];
+      const bool step_gemm = L.kind == K_TRSML || L.kind == K_GEMM;
+      if (L.side) {
+        if (!step_gemm || L.grp != (int)lv + 1) return fail(kSchedErrState, "internal: a side launch of another kind or level");
+        for (int64_t j = L.off; j < L.off + L.cnt; ++j) {
+          const GemmRec& g = S.gt[j];
+          Pos c{}, a{};
+          bool ok = where(g, g.C, c) && S.hsn[g.front].mode == 2 && c.row >= c.oend && c.row + g.m <= c.M &&
+                    c.col + g.n <= c.oend;
+          if (ok && L.kind == K_GEMM) ok = where(g, g.A, a) && a.row == c.row && a.oend == c.oend;
+          if (!ok) return fail(kSchedErrState, "internal: a side task reaches above its outer block's end");
+          if (!pend[g.front]) {
+            pend[g.front] = 1;
+            plist.push_back(g.front);
+          }
+        }
+        plevel = lv;
+        continue;
+      }
+      if (plist.empty()) continue;
+      if (fac_joins_side(L.kind)) {
+        for (const int32_t f : plist) pend[f] = 0;
+        plist.clear();
+        continue;
+      }
+      if (lv != plevel) return fail(kSchedErrState, "internal: side launches not joined before the next level");
+      if (!step_gemm) continue;
+      for (int64_t j = L.off; j < L.off + L.cnt; ++j) {
+        const GemmRec& g = S.gt[j];
+        Pos c{};
+        if (g.front < 0 || !pend[g.front]) continue;
+        if (!where(g, g.C, c) || c.row + g.m > c.oend)
+          return fail(kSchedErrState, "internal: a main-stream task writes rows a pending side launch owns");
+      }
+    }
   }
   // End of an outer block: the deferred row swaps on the columns outside it, its U rows on every
   // column right of it (sub-panel by sub-panel, k_urows or GEMM-form TRSM), then the trailing
@@ -1449,13 +1558,16 @@ struct Builder {
     levels();
     f22g.assign(P.nsup, 0);
     for (int l = 0; l < P.nlevels && err.empty(); ++l) {
+      cur_level = l;
       choose_f22_gather(l);
       assembly(l, f22_exchange(l));
       small_fronts(l);
       if (err.empty()) blocked_fronts(l);
       if (!err.empty()) break;
       for (const int32_t t : dfront[l]) shared_front(t);   // in front order on every rank
+      lvl_end.push_back(S.fac.size());
     }
+    if (err.empty()) lside_check();
     for (int l = 0; l < P.nlevels && err.empty(); ++l) {
       solve_level(l);
       for (const int32_t t : dfront[l]) shared_forward(t);

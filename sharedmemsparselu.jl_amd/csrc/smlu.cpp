@@ -302,6 +302,8 @@ double smlu_stat(const smlu_handle* h, const char* key) {
   if (k == "f22_gather_fronts") return (double)h->sch.f22_gather_fronts;
   if (k == "f22_gather_entries") return h->sch.f22_gather_entries;
   if (k == "gemm128_launches") return (double)h->sch.gemm128_launches;
+  if (k == "side_launches") return (double)h->sch.side_launches;
+  if (k == "side_rows") return (double)h->sch.side_rows;
   if (k == "vendor_calls") return 0.0;   // no vendor GEMM path (round 5)
   if (k.rfind("ms_", 0) == 0) {
     std::string name = k.substr(3);

@@ -16,6 +16,7 @@ Tune tune() {
     if (const char* e = std::getenv("SMLU_FULLPIV_NS")) v.fullpiv_ns = std::atoll(e);
     if (const char* e = std::getenv("SMLU_F22_GATHER_NU")) v.f22_gather_nu = std::atoll(e);
     if (const char* e = std::getenv("SMLU_F22_GATHER_CH")) v.f22_gather_ch = std::atoll(e);
+    if (const char* e = std::getenv("SMLU_LSIDE_MIN")) v.lside_min = std::max<long long>(0, std::atoll(e));
     if (const char* e = std::getenv("SMLU_SWEEP_SPIN")) v.sweep_spin = std::atoi(e);
     if (const char* e = std::getenv("SMLU_SOLVE_STEPS")) v.solve_steps = std::atoi(e) == 1;
     v.no_graph = std::getenv("SMLU_NO_GRAPH") != nullptr;
