@@ -35,6 +35,7 @@ extern "C" {
 #define SMLU_OK                 0
 #define SMLU_SINGULAR           1   /* zero pivot column (UMFPACK SingularException, src/SharedMemSparseLU.jl:74) */
 #define SMLU_PIVOT_WEAK         2   /* a pivot failed the threshold test (growth > 1/pivot_tol) */
+#define SMLU_NOT_CONVERGED      3   /* smlu_solve_gmres*: stopped short of rtol; x holds the last iterate */
 #define SMLU_ERR_ARG          (-1)  /* bad argument / DimensionMismatch (src/SharedMemSparseLU.jl:288-290) */
 #define SMLU_ERR_PATTERN      (-2)  /* refactor called with a different sparsity pattern, or a given L/U
                                        pattern outside the structural fill of (Rs.*A)[p,q] */
@@ -214,6 +215,58 @@ int smlu_logabsdet_z(smlu_handle* h, double* logabs, double phase[2]);
 #define SMLU_NORM_INF 2
 int smlu_rcond(smlu_handle* h, int norm, double* rcond, double* anorm, double* ainvnorm);
 
+/* Solve with stale factors: restarted, right-preconditioned GMRES(m) for op(A') x = b, where A' has the
+ * handle's sparsity pattern and the caller's values and the preconditioner is the handle's current
+ * factorization M = LU ~ op(A) (PARDISO's "iterate with the previous factorization"; what MUMPS and
+ * UMFPACK users do by hand on the host; not in the reference).  A caller whose values moved a little
+ * since the last smlu_refactor gets a solution to rtol without refactoring; with nzval = NULL (the
+ * handle's own current values) it is GMRES-based refinement of the factored system, the stronger
+ * remedy for a weak-pivot factorization than smlu_opts.refine's classical steps.
+ *   op      SMLU_OP_N, SMLU_OP_T or SMLU_OP_H (a real handle: H is T); anything else: SMLU_ERR_ARG.
+ *   nzval   nnz(A) doubles in A's original CSC order, as smlu_refactor[_device]; NULL: the handle's.
+ *   b, x    n doubles; x == b allowed (the handle keeps its own copy of b).
+ *   opts    NULL: the defaults of smlu_gmres_default_opts (rtol 1e-10, restart 30, maxit 200).
+ *           restart in 1..32, maxit >= 1 (it counts Arnoldi steps), rtol finite and >= 0: else SMLU_ERR_ARG.
+ *   info    may be NULL.
+ * The _device form reads caller memory after the caller's stream (smlu_set_stream) and returns with x
+ * complete.  All n-vectors stay on the device; the host reads one 64-byte record per iteration.
+ * The algorithm is fixed, so results are reproducible (two identical calls are bitwise equal; the
+ * host and device forms agree bitwise): x0 = 0; each cycle starts from the true residual
+ * r = b - op(A') x, computed on the device with its 2-norm; an Arnoldi step is one plain factor solve
+ * z = M^-1 v_j (never refined, whatever smlu_opts.refine says, as smlu_rcond), the product
+ * w = op(A') z and classical Gram-Schmidt run twice against v_0..v_j; the Hessenberg column, the
+ * Givens rotations and the residual estimate |g_{j+1}| are updated on the device.  A cycle ends when
+ * the estimate is <= rtol ||b||_2, after `restart` steps, at maxit, or on a breakdown h_{j+1,j} = 0;
+ * then x += M^-1 (V y), one more factor solve: info->solves == iters + cycles.  Convergence is
+ * declared only on the true residual, relres = ||b - op(A') x||_2 / ||b||_2 <= rtol.  The run stops
+ * with SMLU_NOT_CONVERGED (positive: x holds the last iterate, info is filled) when maxit is reached,
+ * when a non-finite norm appears, or when a cycle that ended on its estimate leaves a true residual
+ * above rtol that is not below half the previous cycle's (stagnation).  b = 0 gives x = 0, converged,
+ * 0 iterations.
+ *   info: converged (1 / 0), iters (Arnoldi steps), cycles, solves (factor solves), relres (true, of
+ *   the returned x), relres_est (the last estimate / ||b||), berr (componentwise backward error
+ *   max_i |r_i| / (|op(A')||x| + |b|)_i of the returned x against A'), bnorm (||b||_2).
+ * The handle stays as it was: its values, factors, determinant and rcond caches and chunked layout
+ * are untouched, and a later smlu_solve is bitwise what it was before.  Work buffers (restart + 1
+ * basis columns of leading dimension n rounded up to even, a few n-vectors, the partials) belong to
+ * the handle: allocated on first use, grown when restart grows, freed with it; SMLU_ERR_ALLOC when
+ * they do not fit.  SMLU_ERR_STATE: no numeric factorization (none yet, or a singular one), a
+ * partitioned handle (smlu_dist_*), or a ComplexF64 handle (out of scope: the complex Krylov process
+ * on the real-equivalent factors is not implemented).  smlu_stat: "gmres_iters", "gmres_cycles",
+ * "gmres_solves", "gmres_ms_last" (the last call); transposed preconditioner solves count in
+ * "solve_trans_passes".  The preconditioner solves are the library's ordinary solve passes, so, as
+ * after smlu_rcond, "solve_ms_last" holds the last of them and a profiling handle's "ms_solve" has
+ * grown; and each of them ends in its own stream synchronisation and sweep-status read, as every
+ * solve does: the one record per iteration is what the Krylov process itself adds to that. */
+typedef struct smlu_gmres_opts { double rtol; int32_t restart; int32_t maxit; } smlu_gmres_opts;
+typedef struct smlu_gmres_info { int32_t converged, iters, cycles, solves;
+                                 double relres, relres_est, berr, bnorm; } smlu_gmres_info;
+void smlu_gmres_default_opts(smlu_gmres_opts* opts);
+int smlu_solve_gmres(smlu_handle* h, int op, const double* nzval, const double* b, double* x,
+                     const smlu_gmres_opts* opts, smlu_gmres_info* info);
+int smlu_solve_gmres_device(smlu_handle* h, int op, const double* d_nzval, const double* d_b, double* d_x,
+                            const smlu_gmres_opts* opts, smlu_gmres_info* info);
+
 /* ParallelSparseLU(A::SparseMatrixCSC{Float64,Int32}) — Int32 index arrays;
  * converted to the Int64 path on the host. */
 int smlu_create_i32(int64_t n, const int32_t* colptr, const int32_t* rowval, const double* nzval,
@@ -311,7 +364,7 @@ int64_t     smlu_last_error_col(const smlu_handle* h);      /* column of a zero/
  * "factor_bytes","scratch_bytes","launches","analysis_ms","refactor_ms_last","solve_ms_last",
  * "growth_max","dense_flops","gemm_flops","ms_gemm","ms_panel","ms_trsm","ms_assemble",
  * "ms_small","ms_solve","solve_trans_passes","rcond_solves","rcond_solves_fwd","rcond_solves_adj",
- * "rcond_iters","logabsdet_evals".
+ * "rcond_iters","logabsdet_evals","gmres_iters","gmres_cycles","gmres_solves","gmres_ms_last".
  * Returns NaN for an unknown key. */
 double smlu_stat(const smlu_handle* h, const char* key);
 

@@ -128,6 +128,12 @@ constexpr int kMultiRhs = 16;   // right-hand sides per solve launch
 // one workgroup's partial result
 constexpr int kDgMaxBlocks = 256;
 constexpr int kDgPartWords = 8;
+// kernels_krylov.hip: the longest restart (basis columns a pass holds in registers), the doubles of
+// one workgroup's partial (a column each, and two spare) and of the small problem's device state
+constexpr int kKryMaxRestart = 32;
+constexpr int kKryPartStride = kKryMaxRestart + 2;
+constexpr int kKryStateWords = 1 + 2 * kKryMaxRestart + kKryMaxRestart * kKryMaxRestart + 2 * kKryMaxRestart +
+                               (kKryMaxRestart + 1) + kKryMaxRestart;
 #ifndef SMLU_SWEEP_WK
 #define SMLU_SWEEP_WK 4
 #endif

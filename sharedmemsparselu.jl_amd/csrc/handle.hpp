@@ -5,6 +5,7 @@
 //   solve.cpp     (solves, refinement, chunked layout)     export.cpp  (factor export, pattern hand-over)
 //   complex.cpp   (ComplexF64 handles)                     dist.cpp    (RCCL, partitioned handles)
 //   smlu.cpp      (create / destroy / stats / plan API)    diag.cpp    (determinant, condition estimate)
+//   krylov.cpp    (GMRES preconditioned by the factors)
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -115,6 +116,14 @@ hipError_t launch_dg_norm(hipStream_t, bool, bool, int64_t, const int64_t*, cons
 hipError_t launch_dg_vec(hipStream_t, bool, int64_t, int, int64_t, double*);
 hipError_t launch_dg_sign(hipStream_t, bool, int64_t, const double*, double*, int, void*, long long*, long long);
 hipError_t launch_dg_argmax(hipStream_t, bool, int64_t, const double*, int64_t, void*, long long*, long long);
+// kernels_krylov.hip: GMRES on the factors (the residual and the Arnoldi step end in the 64-byte record rec)
+hipError_t launch_kry_spmv(hipStream_t, bool, int64_t, const int64_t*, const int32_t*, const int32_t*, const int64_t*,
+                           const int32_t*, const double*, const double*, const void*, double*, double*);
+hipError_t launch_kry_resid(hipStream_t, bool, int64_t, const int64_t*, const int32_t*, const int32_t*, const int64_t*,
+                            const int32_t*, const double*, const double*, const double*, double*, double*, void*,
+                            long long*, long long);
+hipError_t launch_kry_arnoldi(hipStream_t, int64_t, int64_t, int, double*, double*, double*, void*, long long*, long long);
+hipError_t launch_kry_update(hipStream_t, int64_t, int64_t, int, const double*, void*, double*);
 }  // namespace smlu
 
 using namespace smlu;
@@ -306,6 +315,15 @@ struct smlu_handle {
   double det_logabs = 0, det_phase[2] = {1, 0};
   double rc_anorm[2] = {0, 0}, rc_ainv[2] = {0, 0};
   int64_t logabsdet_evals = 0, rcond_iters = 0, rcond_solves = 0, rcond_solves_fwd = 0, rcond_solves_adj = 0;
+  // GMRES preconditioned by the factors (krylov.cpp): buffers allocated on first use and grown with
+  // the restart length; kry_cols basis columns of leading dimension n rounded up to even
+  DBuf<double> kry_V, kry_z, kry_w, kry_b, kry_x, kry_vals, kry_part, kry_state;
+  DBuf<long long> kry_rec;
+  int kry_cols = 0;         // basis columns allocated and cleared
+  bool kry_ready = false;   // the vectors, partials, state and record are all allocated and cleared
+  long long kry_seq = 0;
+  int64_t gmres_iters = 0, gmres_cycles = 0, gmres_solves = 0;   // of the last call
+  double gmres_ms = 0;
   ~smlu_handle() { release_all(); }
   void release_buffers() {
     if (stream) (void)hipSetDevice(device);
@@ -332,6 +350,11 @@ struct smlu_handle {
     dg_xi.free();
     dg_part.free();
     dg_rec.free();
+    DBuf<double>* k[] = {&kry_V, &kry_z, &kry_w, &kry_b, &kry_x, &kry_vals, &kry_part, &kry_state};
+    for (auto* b : k) b->free();
+    kry_rec.free();
+    kry_cols = 0;
+    kry_ready = false;
     xtasks.free();
     aents.free();
     ftiles.free();

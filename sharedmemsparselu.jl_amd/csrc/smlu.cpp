@@ -249,6 +249,11 @@ double smlu_stat(const smlu_handle* h, const char* key) {
   if (k == "rcond_solves_adj") return (double)h->rcond_solves_adj;
   if (k == "rcond_iters") return (double)h->rcond_iters;
   if (k == "logabsdet_evals") return (double)h->logabsdet_evals;
+  // the last smlu_solve_gmres*: Arnoldi steps, cycles, factor solves (steps + cycles) and wall time
+  if (k == "gmres_iters") return (double)h->gmres_iters;
+  if (k == "gmres_cycles") return (double)h->gmres_cycles;
+  if (k == "gmres_solves") return (double)h->gmres_solves;
+  if (k == "gmres_ms_last") return h->gmres_ms;
   if (k == "sweep_status") {     // the device flag itself (cleared whenever a solve reports it)
     int32_t v = 0;
     if (h->sstatus.p && hipMemcpy(&v, h->sstatus.p, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;

@@ -3,7 +3,7 @@
 # its argument count).  See INTEGRATION.md.
 module SharedMemSparseLU
 
-export ParallelSparseLU, cleanup_ParallelSparseLU!, allocate_shared
+export ParallelSparseLU, cleanup_ParallelSparseLU!, allocate_shared, gmres!
 
 using LinearAlgebra, SparseArrays, Libdl
 import LinearAlgebra: ldiv!, lu!
@@ -220,6 +220,34 @@ function LinearAlgebra.cond(F::ParallelSparseLU, p::Real)
     check(ccall((:smlu_rcond, libsmlu), Int32, (Ptr{Cvoid}, Int32, Ref{Float64}, Ptr{Float64}, Ptr{Float64}),
                 F.handle, Int32(p == 1 ? 1 : 2), r, C_NULL, C_NULL), F.handle)
     return r[] == 0 ? Inf : inv(r[])
+end
+
+# gmres!(x, F, A, b): solve A x = b with the factors F already holds, when A's values have moved a
+# little since lu!(F, .): restarted GMRES preconditioned by those factors, all on the GPU
+# (smlu_solve_gmres; PARDISO's "iterate with the previous factorization").  A must have F's pattern;
+# A = nothing takes the values F factored (GMRES-based refinement).  Returns (x, info); a run that
+# stops short of rtol (status 3) does not throw: info.converged == 0 and x is the last iterate.
+# The two structs must match the header's GMRES option and result records field for field.
+mutable struct GmresOpts; rtol::Float64; restart::Int32; maxit::Int32; end
+mutable struct GmresInfo
+    converged::Int32; iters::Int32; cycles::Int32; solves::Int32
+    relres::Float64; relres_est::Float64; berr::Float64; bnorm::Float64
+end
+function gmres!(x::AbstractVector, F::ParallelSparseLU{Float64}, A::Union{SparseMatrixCSC{Float64},Nothing},
+                b::AbstractVector; rtol=1e-10, restart=30, maxiter=200)
+    length(x) == length(b) == F.n || throw(DimensionMismatch("x, b and F sizes differ"))
+    A === nothing || (A.colptr == F.colptr && A.rowval == F.rowval) ||
+        throw(ArgumentError("gmres!: A must have the sparsity pattern F was created with"))
+    o = GmresOpts(rtol, restart, maxiter)
+    info = GmresInfo(0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0)
+    bb = b isa Vector{Float64} ? b : Vector{Float64}(b)
+    xx = x isa Vector{Float64} ? x : similar(bb)
+    rc = ccall((:smlu_solve_gmres, libsmlu), Int32,
+               (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{GmresOpts}, Ref{GmresInfo}),
+               F.handle, Int32(0), A === nothing ? C_NULL : A.nzval, bb, xx, o, info)
+    rc < 0 && check(rc, F.handle)
+    xx === x || copyto!(x, xx)
+    return x, info
 end
 
 function _trisolve!(upper::Bool, F::ParallelSparseLU{Tf}, x::AbstractVector) where {Tf}

@@ -23,6 +23,7 @@ vp = ctypes.c_void_p
 SMLU_OK = 0
 SMLU_SINGULAR = 1
 SMLU_PIVOT_WEAK = 2
+SMLU_NOT_CONVERGED = 3
 SMLU_ERR_ARG = -1
 SMLU_ERR_PATTERN = -2
 SMLU_ERR_ALLOC = -3
@@ -61,6 +62,15 @@ class SmluOpts(ctypes.Structure):
     ]
 
 
+class SmluGmresOpts(ctypes.Structure):
+    _fields_ = [("rtol", f64), ("restart", i32), ("maxit", i32)]
+
+
+class SmluGmresInfo(ctypes.Structure):
+    _fields_ = [("converged", i32), ("iters", i32), ("cycles", i32), ("solves", i32),
+                ("relres", f64), ("relres_est", f64), ("berr", f64), ("bnorm", f64)]
+
+
 # exported symbols and their signatures (restype, argtypes); the CPU test-suite checks that
 # every function declared in include/smlu.h is present here and in the .so
 SIGNATURES = {
@@ -88,6 +98,10 @@ SIGNATURES = {
     "smlu_logabsdet": (i32, [vp, f64p, f64p]),
     "smlu_logabsdet_z": (i32, [vp, f64p, f64p]),
     "smlu_rcond": (i32, [vp, i32, f64p, f64p, f64p]),
+    "smlu_gmres_default_opts": (None, [ctypes.POINTER(SmluGmresOpts)]),
+    "smlu_solve_gmres": (i32, [vp, i32, vp, vp, vp, ctypes.POINTER(SmluGmresOpts), ctypes.POINTER(SmluGmresInfo)]),
+    "smlu_solve_gmres_device": (i32, [vp, i32, vp, vp, vp, ctypes.POINTER(SmluGmresOpts),
+                                      ctypes.POINTER(SmluGmresInfo)]),
     "smlu_create_i32": (i32, [i64, vp, vp, vp, ctypes.POINTER(SmluOpts), ctypes.POINTER(vp)]),
     "smlu_create_z": (i32, [i64, vp, vp, vp, ctypes.POINTER(SmluOpts), ctypes.POINTER(vp)]),
     "smlu_refactor_z": (i32, [vp, vp]),

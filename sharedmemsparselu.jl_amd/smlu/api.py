@@ -10,6 +10,7 @@ ldiv!(x, F', b)                     ldiv_(x, F, b, trans="C")     (not in the re
 lsolve!(F, x), rsolve!(F, x)        lsolve_(F, x), rsolve_(F, x)  :349-392
 logabsdet(F), det(F), logdet(F)     F.logabsdet() F.det() F.logdet()  (not in the reference)
 cond(F, 1), cond(F, Inf)            F.condest("1"|"inf"), F.rcond()   (not in the reference)
+gmres!(x, F, A, b)                  F.gmres(b, values=A)          (not in the reference)
 F.L F.U F.p F.q F.Rs                F.L F.U F.p F.q F.Rs          :45-52 (0-based here)
 cleanup_ParallelSparseLU!(F)        cleanup_ParallelSparseLU_(F)  :31 (exported, undefined there)
 DimensionMismatch                   DimensionMismatch             :288-290
@@ -24,7 +25,9 @@ All numerics run on the MI355X through libsmlu.so; nothing here computes factors
 """
 from __future__ import annotations
 
+import collections
 import ctypes
+import math
 
 import numpy as np
 import scipy.sparse as sp
@@ -45,7 +48,7 @@ class SingularException(np.linalg.LinAlgError):
 
 
 class SmluError(RuntimeError):
-    pass
+    code = None   # the library's status code, when the error came from a C call
 
 
 def _csc(A):
@@ -76,9 +79,56 @@ def _norm(norm):
         raise ValueError(f'norm must be "1" or "inf", got {norm!r}') from None
 
 
+GmresInfo = collections.namedtuple(
+    "GmresInfo", "converged iters cycles solves relres relres_est berr bnorm status")
+GmresInfo.__doc__ = """What smlu_solve_gmres* reports: converged (bool), iters (Arnoldi steps), cycles,
+solves (factor solves = iters + cycles), relres (true ||b - op(A')x|| / ||b|| of the returned x),
+relres_est (the last estimate), berr (componentwise backward error), bnorm, status (the C return code:
+0 or SMLU_NOT_CONVERGED)."""
+
+
+def _gmres_opts(trans, rtol, restart, maxiter):
+    """(op, SmluGmresOpts) after the argument checks of smlu_solve_gmres*, raised as ValueError
+    before any handle is looked at."""
+    op = _op(trans)
+    for name, v in (("restart", restart), ("maxiter", maxiter)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    if not 1 <= restart <= 32:
+        raise ValueError(f"restart must be in 1..32, got {restart!r}")
+    if maxiter < 1:
+        raise ValueError(f"maxiter must be at least 1, got {maxiter!r}")
+    try:
+        rt = float(rtol)
+    except (TypeError, ValueError):
+        raise ValueError(f"rtol must be a finite number >= 0, got {rtol!r}") from None
+    if not (math.isfinite(rt) and rt >= 0.0):
+        raise ValueError(f"rtol must be a finite number >= 0, got {rtol!r}")
+    return op, C.SmluGmresOpts(rt, int(restart), int(maxiter))
+
+
+def _device_f64(name, t, size):
+    """A torch tensor handed to a *_device entry point as `size` doubles must be that: float64, on a
+    GPU, contiguous, `size` elements (a raw pointer int, or None, is taken as it is)."""
+    if t is None or not hasattr(t, "data_ptr"):
+        return
+    import torch
+    if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+        raise TypeError(f"`{name}` must be a contiguous float64 tensor on the GPU")
+    if t.numel() != size:
+        raise DimensionMismatch(f"`{name}` has {t.numel()} elements, expected {size}")
+
+
+def _gmres_info(rc, ci):
+    return GmresInfo(bool(ci.converged), ci.iters, ci.cycles, ci.solves, ci.relres, ci.relres_est, ci.berr,
+                     ci.bnorm, rc)
+
+
 def _check(rc, h=None):
     if rc < 0:
-        raise SmluError(f"libsmlu error {rc}: {C.last_error(h)}")
+        e = SmluError(f"libsmlu error {rc}: {C.last_error(h)}")
+        e.code = rc
+        raise e
     return rc
 
 
@@ -369,6 +419,67 @@ class ParallelSparseLU:
         _norm(norm)
         _, an, ai = ParallelSparseLU.rcond(self, norm, parts=True)
         return an * ai if an * ai > 0 else float("inf")
+
+    # ---- solve with stale factors (smlu_solve_gmres*) ----
+    def gmres(self, b, values=None, trans="N", rtol=1e-10, restart=30, maxiter=200, x=None):
+        """Solve op(A') x = b by restarted GMRES(restart) preconditioned by the current factors, all
+        on the GPU (smlu_solve_gmres): A' has F's pattern and `values` (an nnz array in A's CSC order,
+        or a scipy matrix of the same pattern; None: the values F holds, i.e. GMRES-based refinement).
+        trans as ldiv_.  Returns (x, info); x is written into the given array when one is passed
+        (it may be b).  Non-convergence does not raise: info.converged is False and x the last
+        iterate.  F itself -- values, factors, caches -- is left as it was."""
+        op, o = _gmres_opts(trans, rtol, restart, maxiter)
+        if self.is_complex:   # out of scope, as in the library (smlu_solve_gmres: SMLU_ERR_STATE)
+            e = SmluError(f"libsmlu error {C.SMLU_ERR_STATE}: gmres: ComplexF64 handles are not supported")
+            e.code = C.SMLU_ERR_STATE
+            raise e
+        if len(b) != self.n:
+            raise DimensionMismatch(f"`b` does not have same size as F: length(b)={len(b)}, F.n={self.n}")
+        vals = None
+        if values is not None:
+            if sp.issparse(values):
+                A = _csc(values)
+                if A.shape != (self.m, self.n) or A.nnz != self._rowval.size or \
+                        not np.array_equal(A.indptr, self._colptr) or not np.array_equal(A.indices, self._rowval):
+                    raise ValueError("gmres: `values` must have the sparsity pattern F was created with")
+                values = A.data
+            vals = np.ascontiguousarray(values, dtype=np.float64)
+            if vals.shape != (self._rowval.size,):
+                raise DimensionMismatch(f"`values` has shape {vals.shape}, nnz(A)={self._rowval.size}")
+        bb = np.ascontiguousarray(b, dtype=np.float64)
+        if x is None:
+            x = np.empty(self.n)
+        elif len(x) != self.n:
+            raise DimensionMismatch(f"`x` does not have same size as F: length(x)={len(x)}, F.n={self.n}")
+        xx = x if (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.flags.c_contiguous) \
+            else np.empty(self.n)
+        ci = C.SmluGmresInfo()
+        rc = _check(C.lib().smlu_solve_gmres(self._h, op, C.ptr(vals), C.ptr(bb), C.ptr(xx), ctypes.byref(o),
+                                             ctypes.byref(ci)), self._h)
+        if xx is not x:
+            x[:] = xx
+        return x, _gmres_info(rc, ci)
+
+    def gmres_device(self, d_x, d_b, d_values=None, trans="N", rtol=1e-10, restart=30, maxiter=200):
+        """gmres on device vectors (torch tensors or raw pointer ints; d_x may be d_b): d_values holds
+        nnz doubles in A's CSC order on the device, None: the values F holds.  Returns info
+        (smlu_solve_gmres_device, ordered after the stream that produced d_b)."""
+        op, o = _gmres_opts(trans, rtol, restart, maxiter)
+        if self.is_complex:
+            e = SmluError(f"libsmlu error {C.SMLU_ERR_STATE}: gmres: ComplexF64 handles are not supported")
+            e.code = C.SMLU_ERR_STATE
+            raise e
+        for name, t, size in (("d_x", d_x, self.n), ("d_b", d_b, self.n), ("d_values", d_values, self._rowval.size)):
+            _device_f64(name, t, size)
+        px = d_x.data_ptr() if hasattr(d_x, "data_ptr") else int(d_x)
+        pb = d_b.data_ptr() if hasattr(d_b, "data_ptr") else int(d_b)
+        pv = None if d_values is None else \
+            ctypes.c_void_p(d_values.data_ptr() if hasattr(d_values, "data_ptr") else int(d_values))
+        ci = C.SmluGmresInfo()
+        with C.caller_stream(self._h, d_b):
+            rc = _check(C.lib().smlu_solve_gmres_device(self._h, op, pv, ctypes.c_void_p(pb), ctypes.c_void_p(px),
+                                                        ctypes.byref(o), ctypes.byref(ci)), self._h)
+        return _gmres_info(rc, ci)
 
     def close(self):
         h = getattr(self, "_h", None)
