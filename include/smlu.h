@@ -144,7 +144,9 @@ int smlu_residual_device(smlu_handle* h, const double* d_x, const double* d_b, d
 
 /* ldiv! with nrhs right-hand sides: column j of B (ldb >= n) -> column j of X (ldx >= n),
  * host memory, X == B allowed.  The reference's ldiv! is generic over the vector type
- * (src/SharedMemSparseLU.jl:286); multiple RHS are SURVEY §8f-4. */
+ * (src/SharedMemSparseLU.jl:286); multiple RHS are SURVEY §8f-4.  "solve_passes" counts the forward
+ * solve passes run on the handle so far, refinement corrections included: one per single-vector
+ * solve, one per batch of up to 16 columns (the forward twin of "solve_trans_passes"). */
 int smlu_solve_multi(smlu_handle* h, int64_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx);
 
 /* Same with device pointers. */
@@ -363,7 +365,7 @@ int64_t     smlu_last_error_col(const smlu_handle* h);      /* column of a zero/
  * "n","nnzA","nsuper","nlevels","nnzL","nnzU","nnzLU","flops","upd","front_max","ns_max",
  * "factor_bytes","scratch_bytes","launches","analysis_ms","refactor_ms_last","solve_ms_last",
  * "growth_max","dense_flops","gemm_flops","ms_gemm","ms_panel","ms_trsm","ms_assemble",
- * "ms_small","ms_solve","solve_trans_passes","rcond_solves","rcond_solves_fwd","rcond_solves_adj",
+ * "ms_small","ms_solve","solve_passes","solve_trans_passes","rcond_solves","rcond_solves_fwd","rcond_solves_adj",
  * "rcond_iters","logabsdet_evals","gmres_iters","gmres_cycles","gmres_solves","gmres_ms_last".
  * Returns NaN for an unknown key. */
 double smlu_stat(const smlu_handle* h, const char* key);

@@ -262,7 +262,8 @@ struct smlu_handle {
   int32_t bad_info_word = 0;
   int64_t sweep_timeouts = 0;   // solves re-run on the per-block schedule after a sweep wait timed out
   int64_t trans_passes = 0;     // executions of the transposed pass pair (U^T then L^T), one per batch of columns
-  int sweep_spin = 1 << 22;     // polls before a sweep wait gives up (SMLU_SWEEP_SPIN; 0 = always, tests)
+  int64_t solve_passes = 0;     // executions of the forward solve (run_solve_dev, ldiv), one per batch of columns
+  int sweep_spin = 1 << 22;    // polls before a sweep wait gives up (SMLU_SWEEP_SPIN; 0 = always, tests)
   DBuf<double> bstash;          // the solve's input when the final step overwrites it (x === b, lsolve!/rsolve!)
   std::vector<std::pair<int, hipGraphExec_t>> sol_execs;   // captured solve sweeps, keyed by mode/rhs count
   std::vector<hipGraphExec_t> fac_execs;   // one captured graph per factor segment

@@ -239,6 +239,9 @@ double smlu_stat(const smlu_handle* h, const char* key) {
   if (k == "sweep_timeouts") {   // solves re-run on the per-block schedule after a sweep wait timed out
     return (double)h->sweep_timeouts;
   }
+  if (k == "solve_passes") {   // forward solve passes (ldiv) run so far, one per batch of columns
+    return (double)h->solve_passes;
+  }
   if (k == "solve_trans_passes") {   // transposed pass pairs (U^T then L^T) run so far, one per batch of columns
     return (double)h->trans_passes;
   }

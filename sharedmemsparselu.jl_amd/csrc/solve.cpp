@@ -196,6 +196,7 @@ int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode, int nr
   // only the permutation kernels see the caller's b and x.
   int rc = run_graphed(h, h->nranks == 1 && !tune().no_graph, mode * 256 + rh.n, [&] { return sweeps(steps); });
   if (rc != SMLU_OK) return rc;
+  if (mode == 0) ++h->solve_passes;   // a sweep-timeout re-run below is the same pass
   HIPCHK(finish());
   HIPCHK(tm.end(stop));
   HIPCHK(hipStreamSynchronize(st));
@@ -371,6 +372,7 @@ static int solve_multi_dev(smlu_handle* h, int64_t nrhs, const double* d_B, int6
   }
   h->refine_steps = 0;
   h->refine_resid = -1;
+  h->refine_berr = -1;
   double ms = 0;
   for (int64_t j = 0; j < nrhs; j += kMultiRhs) {
     const int nb = (int)std::min<int64_t>(kMultiRhs, nrhs - j);

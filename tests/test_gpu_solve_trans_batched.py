@@ -8,7 +8,12 @@ test_gpu_solve_trans.py, the smallest that reach each kernel: micro / tiny / sma
 n = 1, 2 (golden fixtures), large fronts with a partial last block, nu = 0 at the root and the
 side-stream fork (poisson3d(28)), tall fronts (poisson2d(300)), row exchanges in every tile
 (tile_pivoting_matrix), a complex handle and the refinement fallback.  Widths 2 .. 33 cross every
-kernel instantiation (4, 8, 16 wide), partial batches and more than one batch."""
+kernel instantiation (4, 8, 16 wide), partial batches and more than one batch.
+
+Under the default options a non-dominant matrix is refined and the batch call goes column by column:
+there the bitwise comparison is the single-vector solve against itself.  check_unrefined_batches
+therefore repeats the non-dominant cases on a handle created with refine=0, counts the passes, and
+holds a batch against unrefined host solves from the exported factors (tests/_batch_ref.py)."""
 import ctypes
 
 import numpy as np
@@ -20,7 +25,8 @@ import smlu
 from smlu import _lib as C
 from smlu import matrices as mats
 
-from _parity import tile_pivoting_matrix
+from _batch_ref import assert_batch_against_oracle, complex_tile_150, stale_slot_sequence
+from _parity import DENSE_TOL, tile_pivoting_matrix
 from test_gpu_solve_trans import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -217,13 +223,38 @@ def test_neighbouring_forward_batches(p12):
 
 
 # ---- every kernel --------------------------------------------------------------------------------
+def check_unrefined_batches(A, trans="T", label="", tol=None, **handle_kw):
+    """A second handle with refine=0: under the default options a non-dominant matrix is refined and
+    solve_trans_multi_dev goes column by column, so check_batch above compares the single-vector
+    solve with itself there.  On this handle a batch of 8 is one pass of the batch kernels, widths 5,
+    9 and 16 are bitwise their single solves, and the 5-wide batch is held against unrefined host
+    solves from the exported factors (tests/_batch_ref.py)."""
+    import torch
+    F = smlu.ParallelSparseLU(A, refine=0, **handle_kw)
+    B8 = _rhs(F.n, 8, 70, F.is_complex)
+    X8 = torch.full_like(B8, float("nan"))
+    p0 = F.stat("solve_trans_passes")
+    F.solve_multi_device(X8, B8, trans=trans)
+    assert F.stat("solve_trans_passes") - p0 == 1
+    B, X = check_batch(F, 5, 71, trans)
+    check_batch(F, 9, 72, trans)
+    check_batch(F, 16, 73, trans)
+    assert_batch_against_oracle(A, F, B.cpu().numpy(), X.cpu().numpy(), trans, tol=tol, label=label)
+    return F
+
+
 @pytest.mark.parametrize("name", GOLDEN)
 def test_golden_fixtures(gpu, name):
     A = load_golden(name)
     F = smlu.ParallelSparseLU(A)
     check_batch(F, 5, 50)
     check_batch(F, 16, 51)
+    dominant = F.stat("dominant") == 1
+    if name in ("dense_13", "fe_5"):
+        assert not dominant
     F.close()
+    if not dominant:
+        check_unrefined_batches(A, "T", name).close()
 
 
 def test_large_fronts_poisson3d_28(gpu):
@@ -247,7 +278,41 @@ def test_row_exchanges_in_every_tile(gpu):
     F = smlu.ParallelSparseLU(A)
     assert not np.array_equal(F.p, F.fronts()["p0"])   # the rowperm scatter is not the identity
     check_batch(F, 8, 55)
+    assert F.stat("dominant") == 0
     F.close()
+    F0 = check_unrefined_batches(A, "T", "tile_pivoting_700_5")
+    assert not np.array_equal(F0.p, F0.fronts()["p0"])
+    F0.close()
+
+
+def test_row_exchanges_in_small_fronts(gpu):
+    """Rows moved inside micro, tiny and small fronts (the matrix of test_gpu_solve_batched.py)."""
+    from test_gpu_solve_batched import HANDLE_KW, moved_rows_by_front_class, pivoting_small_fronts
+    F = check_unrefined_batches(pivoting_small_fronts(), "T", "pivoting_small_fronts", tol=DENSE_TOL,
+                                **HANDLE_KW["pivoting_small_fronts"])
+    classes = moved_rows_by_front_class(F)
+    assert classes["micro"] > 0 and classes["tiny"] > 0 and classes["small"] > 0, classes
+    F.close()
+
+
+def test_stale_slots_transposed(gpu):
+    A = sp.csc_matrix(tile_pivoting_matrix(700, 5))
+    F = smlu.ParallelSparseLU(A, refine=0)   # a fresh handle: nothing was solved on it before
+    stale_slot_sequence(F, "T")
+    F.close()
+
+
+def test_complex_exchanged_pairs(gpu):
+    """A complex handle whose real-equivalent pairs are moved and exchanged inside themselves:
+    transposed and adjoint batches on unrefined factors."""
+    A = complex_tile_150()
+    Ft = check_unrefined_batches(A, "T", "complex_tile_150")
+    assert Ft.is_complex and Ft.stat("cpair") == 1
+    pk = Ft.real_equivalent_factors()["p"]
+    assert int((pk[0::2] > pk[1::2]).sum()) > 0
+    assert not np.array_equal(Ft.p, Ft.fronts()["p0"][0::2] // 2)
+    Ft.close()
+    check_unrefined_batches(A, "C", "complex_tile_150").close()
 
 
 def test_complex_transpose_and_adjoint(gpu):
