@@ -180,6 +180,41 @@ int smlu_solve_trans_multi(smlu_handle* h, int op, int64_t nrhs, const double* B
 int smlu_solve_trans_multi_device(smlu_handle* h, int op, int64_t nrhs, const double* d_B, int64_t ldb,
                                   double* d_X, int64_t ldx);
 
+/* Several right-hand sides with iterative refinement, refined as a batch (dgerfs / dgsrfs refine each
+ * column by its own rule; here up to 16 columns share every pass over the factors and over A).  The
+ * smlu_solve_multi* / smlu_solve_trans_multi* entry points above keep refining column by column.
+ *   op         SMLU_OP_N, SMLU_OP_T or SMLU_OP_H by the rules of smlu_solve_trans* (a real handle: H is
+ *              T; a ComplexF64 handle: 2n interleaved doubles, ldb / ldx counted in doubles).
+ *   max_steps  -1: the handle's own rule (smlu_opts.refine);  0: a plain batch, nothing refined;
+ *              k > 0: up to k corrections per column;  below -1: SMLU_ERR_ARG.
+ *   B, X       column j at B + j*ldb / X + j*ldx, ldb, ldx >= n;  X == B allowed when ldb == ldx.
+ *   info       nrhs entries in host memory (both forms), may be NULL.
+ * Checks as smlu_solve_trans_multi*: SMLU_ERR_ARG for a short leading dimension or a NULL pointer with
+ * nrhs > 0, SMLU_ERR_STATE without a numeric factorization (none yet, or a singular one, as
+ * smlu_logabsdet) or on a partitioned handle; nrhs = 0
+ * returns SMLU_OK and touches nothing.  The _device form reads d_B after the caller's stream
+ * (smlu_set_stream) and returns with d_X complete.
+ * Per batch of up to 16 columns: one batched solve; then, up to the step limit, one batched residual
+ * over the columns still active, one small record read by the host, the stopping rule of the single
+ * refined solve applied to each column, and one batched solve of the surviving columns' residuals at
+ * their own width.  A column that has stopped is not touched again.  Column j of X is bitwise what
+ * smlu_solve_device / smlu_solve_trans_device gives for column j alone on a handle with the same
+ * step limit, and info[j] is what "refine_steps", "refine_berr" and "refine_residual" hold after that
+ * single solve (berr and resid: the last ones measured for the column; -1 when nothing was refined):
+ *   stop  0 not refined;  1 berr <= 2^-51;  2 berr did not halve;  3 the step limit was reached.
+ * smlu_stat: "solve_passes" / "solve_trans_passes" grow by 1 + the largest step count of each batch
+ * (column by column: by the sum of 1 + steps);  "refine_batch_residuals" counts the batched residual
+ * launches run on the handle so far;  "refine_steps", "refine_berr" and "refine_residual" hold the
+ * largest over the call's columns, "solve_ms_last" the sum of the batches' first solves.
+ * Work buffers (a stash of B, the residuals and the corrections, n x 16 doubles each, and 32 norm
+ * words) belong to the handle: allocated on the first refining call, freed with the handle,
+ * SMLU_ERR_ALLOC when they do not fit.  At n = 128^3 the three buffers take 0.8 GB together. */
+typedef struct smlu_refine_info { int32_t steps; int32_t stop; double berr; double resid; } smlu_refine_info;
+int smlu_solve_refined_multi(smlu_handle* h, int op, int max_steps, int64_t nrhs, const double* B, int64_t ldb,
+                             double* X, int64_t ldx, smlu_refine_info* info);
+int smlu_solve_refined_multi_device(smlu_handle* h, int op, int max_steps, int64_t nrhs, const double* d_B,
+                                    int64_t ldb, double* d_X, int64_t ldx, smlu_refine_info* info);
+
 /* logabsdet(F) / det(F) (Julia's LinearAlgebra on an lu object; umfpack_get_determinant; not in the
  * reference): log|det A| of the current factorization and its sign, from the factors on the device
  * -- the diagonal of U, Rs and the parities of the row and column orders and of every front's pivot
@@ -366,7 +401,8 @@ int64_t     smlu_last_error_col(const smlu_handle* h);      /* column of a zero/
  * "factor_bytes","scratch_bytes","launches","analysis_ms","refactor_ms_last","solve_ms_last",
  * "growth_max","dense_flops","gemm_flops","ms_gemm","ms_panel","ms_trsm","ms_assemble",
  * "ms_small","ms_solve","solve_passes","solve_trans_passes","rcond_solves","rcond_solves_fwd","rcond_solves_adj",
- * "rcond_iters","logabsdet_evals","gmres_iters","gmres_cycles","gmres_solves","gmres_ms_last".
+ * "rcond_iters","logabsdet_evals","gmres_iters","gmres_cycles","gmres_solves","gmres_ms_last",
+ * "refine_steps","refine_berr","refine_residual","refine_batch_residuals".
  * Returns NaN for an unknown key. */
 double smlu_stat(const smlu_handle* h, const char* key);
 

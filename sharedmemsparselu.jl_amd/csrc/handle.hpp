@@ -124,6 +124,14 @@ hipError_t launch_kry_resid(hipStream_t, bool, int64_t, const int64_t*, const in
                             long long*, long long);
 hipError_t launch_kry_arnoldi(hipStream_t, int64_t, int64_t, int, double*, double*, double*, void*, long long*, long long);
 hipError_t launch_kry_update(hipStream_t, int64_t, int64_t, int, const double*, void*, double*);
+// kernels_refine.hip: batched refinement (slot s of a launch is column list[s] of X and of the B stash;
+// the residuals and the corrections are compact, slot s at s*n)
+hipError_t launch_residual_batch(hipStream_t, int64_t, const int64_t*, const int32_t*, const int32_t*, const double*,
+                                 const double*, int64_t, const double*, double*, double*, int, const int32_t*);
+hipError_t launch_residual_t_batch(hipStream_t, int64_t, const int64_t*, const int32_t*, const double*, const double*,
+                                   int64_t, const double*, double*, double*, int, int, const int32_t*);
+hipError_t launch_axpy_cols(hipStream_t, int64_t, const double*, double*, int64_t, int, const int32_t*);
+hipError_t launch_refine_record(hipStream_t, const double*, long long*, long long);
 }  // namespace smlu
 
 using namespace smlu;
@@ -220,6 +228,12 @@ struct smlu_handle {
   DBuf<double> ref_b, ref_r, ref_d, ref_nrm;   // iterative refinement (allocated on first use)
   DBuf<int32_t> Acol;                          // column of each A entry (residuals, dominance check)
   DBuf<int64_t> Acolp;                         // A's colptr (device dominance check)
+  // batched refinement (smlu_solve_refined_multi*, on first use): the stash of B, the compact residuals
+  // and corrections (n x kMultiRhs each), the 2 x kMultiRhs norm words and the record the host reads
+  DBuf<double> refm_b, refm_r, refm_d, refm_nrm;
+  DBuf<long long> refm_rec;
+  long long refm_seq = 0;
+  int64_t refine_batch_residuals = 0;   // batched residual launches run so far
   int refine_steps = 0;
   double refine_berr = -1;   // componentwise backward error at the last refinement check
   double refine_resid = -1;
@@ -330,7 +344,8 @@ struct smlu_handle {
     if (stream) (void)hipSetDevice(device);
     release_graphs();
     DBuf<double>* d[] = {&A, &Rs, &store, &scratch, &wrk, &wrk2, &vbuf, &vbufm, &wrkm, &wrk2m, &growth, &ref_b, &ref_r, &ref_d, &ref_nrm,
-                         &tinv, &ch_data, &bstash};
+                         &tinv, &ch_data, &bstash, &refm_b, &refm_r, &refm_d, &refm_nrm};
+    refm_rec.free();
     ch_desc.free();
     ch_p.free();
     ch_q.free();

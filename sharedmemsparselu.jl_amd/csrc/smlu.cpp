@@ -303,6 +303,7 @@ double smlu_stat(const smlu_handle* h, const char* key) {
   if (k == "refine_steps") return (double)h->refine_steps;
   if (k == "refine_residual") return h->refine_resid;
   if (k == "refine_berr") return h->refine_berr;
+  if (k == "refine_batch_residuals") return (double)h->refine_batch_residuals;   // batched residual launches so far
   if (k == "gemm_flops") return h->sch.gemm_flops;
   if (k == "gemm22_flops") return h->sch.gemm22_flops;
   if (k == "gemm_launches") return (double)h->sch.gemm_launches;

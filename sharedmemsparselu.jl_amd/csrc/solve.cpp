@@ -636,6 +636,220 @@ int smlu_solve_trans_multi(smlu_handle* h, int op, int64_t nrhs, const double* B
   return SMLU_OK;
 }
 
+// ---- batched iterative refinement: smlu_solve_refined_multi*  ----------------------
+// solve_refined_by for up to kMultiRhs columns at once: one batched solve, then per round one
+// batched residual over the columns still active, one host read of their norms, the stopping rule
+// per column on the host, and one batched solve of the survivors' residuals at their own width.
+// Every column sees the operations of its single refined solve: the batch kernels give each column
+// its single-vector bits at any width, k_residual_batch the single residual's, and a column that
+// has stopped is not touched again.
+static int ensure_refine_batch(smlu_handle* h, bool trans) {
+  Plan& P = h->plan;
+  if (!h->refm_rec.p) {
+    const size_t nm = (size_t)P.n * kMultiRhs;
+    hipError_t e = h->refm_b.alloc(nm);
+    if (e == hipSuccess) e = h->refm_r.alloc(nm);
+    if (e == hipSuccess) e = h->refm_d.alloc(nm);
+    if (e == hipSuccess) e = h->refm_nrm.alloc(2 * kMultiRhs);
+    if (e == hipSuccess) e = h->refm_rec.alloc(2 * kMultiRhs + 2);
+    if (e == hipSuccess) e = hipMemsetAsync(h->refm_rec.p, 0, (2 * kMultiRhs + 2) * sizeof(long long), h->stream);
+    if (e != hipSuccess) {
+      h->refm_b.free();
+      h->refm_r.free();
+      h->refm_d.free();
+      h->refm_nrm.free();
+      h->refm_rec.free();
+      (void)hipGetLastError();
+      if (e == hipErrorOutOfMemory)
+        return fail(h, SMLU_ERR_ALLOC, "batched refinement: no device memory for its three n x 16 work buffers (" +
+                                           std::to_string(3.0 * 8.0 * nm / 1e9) + " GB)");
+      HIPCHK(e);
+    }
+  }
+  if (trans && !h->Acolp.p) HIPCHK(h->Acolp.upload(P.Acolptr.data(), P.Acolptr.size(), h->stream));
+  return ensure_acol(h);
+}
+
+// The norm words of the round stamped seq (dg_read's rule: both stamps must match).
+static int read_refine_record(smlu_handle* h, long long seq, long long out[2 * kMultiRhs + 2]) {
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int attempt = 0; attempt < 4; ++attempt) {
+    HIPCHK(hipMemcpy(out, h->refm_rec.p, (2 * kMultiRhs + 2) * sizeof(long long), hipMemcpyDeviceToHost));
+    if (out[0] == seq && out[2 * kMultiRhs + 1] == seq) return SMLU_OK;
+    ++h->status_copy_retries;
+  }
+  return fail(h, SMLU_ERR_HIP, "refinement record read back with a wrong sequence stamp (device-to-host copy)");
+}
+
+// One batch of nb <= kMultiRhs columns.  solve(b, ldb, x, ldx, width) is one plain batched solve,
+// residual(x, ldx, b, r, nrm, nact, list) one batched residual launch (b: the stash, leading
+// dimension n).  info: nb entries.  *ms: the plain solve's time.
+template <class SOLVE, class RESID>
+static int refine_batch(smlu_handle* h, int steps, int nb, const double* dB, int64_t ldb, double* dX, int64_t ldx,
+                        smlu_refine_info* info, double* ms, SOLVE&& solve, RESID&& residual) {
+  const int64_t n = h->plan.n;
+  hipStream_t st = h->stream;
+  for (int j = 0; j < nb; ++j) info[j] = smlu_refine_info{0, 0, -1.0, -1.0};
+  if (steps == 0) {
+    int rc = solve(dB, ldb, dX, ldx, nb);
+    *ms = h->solve_ms;
+    return rc;
+  }
+  HIPCHK(hipMemcpy2DAsync(h->refm_b.p, sizeof(double) * n, dB, sizeof(double) * ldb, sizeof(double) * n, (size_t)nb,
+                          hipMemcpyDeviceToDevice, st));   // dB may alias dX
+  int rc = solve(h->refm_b.p, n, dX, ldx, nb);
+  if (rc != SMLU_OK) return rc;
+  *ms = h->solve_ms;
+  const double eps = std::ldexp(1.0, -51);   // 4 unit roundoffs (solve_refined_by)
+  int32_t act[kMultiRhs];
+  double prev[kMultiRhs];
+  int nact = nb;
+  for (int j = 0; j < nb; ++j) {
+    act[j] = j;
+    prev[j] = HUGE_VAL;
+  }
+  for (int it = 0; it < steps && nact > 0; ++it) {
+    HIPCHK(hipMemsetAsync(h->refm_nrm.p, 0, 2 * kMultiRhs * sizeof(double), st));
+    HIPCHK(residual(dX, ldx, h->refm_b.p, h->refm_r.p, h->refm_nrm.p, nact, act));
+    ++h->refine_batch_residuals;
+    const long long seq = ++h->refm_seq;
+    HIPCHK(launch_refine_record(st, h->refm_nrm.p, h->refm_rec.p, seq));
+    long long rec[2 * kMultiRhs + 2];
+    rc = read_refine_record(h, seq, rec);
+    if (rc != SMLU_OK) return rc;
+    int nsurv = 0;
+    for (int s = 0; s < nact; ++s) {
+      const int j = act[s];
+      double nrm, berr;
+      std::memcpy(&nrm, &rec[1 + 2 * j], sizeof nrm);
+      std::memcpy(&berr, &rec[2 + 2 * j], sizeof berr);
+      info[j].resid = nrm;
+      info[j].berr = berr;
+      if (berr <= eps) {
+        info[j].stop = 1;
+      } else if (berr > 0.5 * prev[j]) {
+        info[j].stop = 2;
+      } else {
+        prev[j] = berr;
+        if (nsurv != s)   // the survivor's residual moves down to its new slot
+          HIPCHK(hipMemcpyAsync(h->refm_r.p + (size_t)nsurv * n, h->refm_r.p + (size_t)s * n, sizeof(double) * n,
+                                hipMemcpyDeviceToDevice, st));
+        act[nsurv++] = j;
+      }
+    }
+    nact = nsurv;
+    if (nact == 0) break;
+    rc = solve(h->refm_r.p, n, h->refm_d.p, n, nact);
+    if (rc != SMLU_OK) return rc;
+    HIPCHK(launch_axpy_cols(st, n, h->refm_d.p, dX, ldx, nact, act));
+    for (int s = 0; s < nact; ++s) ++info[act[s]].steps;
+  }
+  for (int s = 0; s < nact; ++s) info[act[s]].stop = 3;   // the step limit
+  HIPCHK(hipStreamSynchronize(st));
+  return SMLU_OK;
+}
+
+// All batches of a call on device pointers (op checked, conj set); info may be NULL.
+static int solve_refined_multi_dev(smlu_handle* h, int op, int conj, int steps, int64_t nrhs, const double* d_B,
+                                   int64_t ldb, double* d_X, int64_t ldx, smlu_refine_info* info) {
+  Plan& P = h->plan;
+  const bool trans = op != SMLU_OP_N;
+  if (steps > 0) {
+    int rc = ensure_refine_batch(h, trans);
+    if (rc != SMLU_OK) return rc;
+  }
+  auto solve = [&](const double* b, int64_t lb, double* x, int64_t lx, int w) {
+    return trans ? run_solve_t_dev(h, conj, b, x, w, lb, lx) : run_solve_dev(h, b, x, 0, w, lb, lx);
+  };
+  auto residual = [&](const double* x, int64_t lx, const double* b, double* r, double* nrm, int nact,
+                      const int32_t* list) {
+    return trans ? launch_residual_t_batch(h->stream, P.n, h->Acolp.p, h->Arow.p, h->A.p, x, lx, b, r, nrm, conj, nact,
+                                           list)
+                 : launch_residual_batch(h->stream, P.n, h->Arowptr.p, h->Arow_ent.p, h->Acol.p, h->A.p, x, lx, b, r,
+                                         nrm, nact, list);
+  };
+  int max_steps = 0;
+  double max_berr = -1, max_resid = -1, ms = 0;
+  for (int64_t j = 0; j < nrhs; j += kMultiRhs) {
+    const int nb = (int)std::min<int64_t>(kMultiRhs, nrhs - j);
+    smlu_refine_info bi[kMultiRhs];
+    double bms = 0;
+    int rc = refine_batch(h, steps, nb, d_B + j * ldb, ldb, d_X + j * ldx, ldx, bi, &bms, solve, residual);
+    if (rc != SMLU_OK) return rc;
+    ms += bms;
+    for (int k = 0; k < nb; ++k) {
+      max_steps = std::max(max_steps, (int)bi[k].steps);
+      max_berr = std::max(max_berr, bi[k].berr);
+      max_resid = std::max(max_resid, bi[k].resid);
+      if (info) info[j + k] = bi[k];
+    }
+  }
+  h->refine_steps = max_steps;
+  h->refine_berr = max_berr;
+  h->refine_resid = max_resid;
+  h->solve_ms = ms;
+  return SMLU_OK;
+}
+
+// argument and state checks of the two entry points (smlu_solve_trans_multi*'s, and max_steps)
+static int refined_multi_check(smlu_handle* h, int op, int max_steps, int64_t nrhs, const double* B, int64_t ldb,
+                               const double* X, int64_t ldx, int* conj, int* steps) {
+  if (!h || nrhs < 0 || (nrhs > 0 && (!B || !X))) return fail(h, SMLU_ERR_ARG, "invalid arguments");
+  if (op != SMLU_OP_N && op != SMLU_OP_T && op != SMLU_OP_H)
+    return fail(h, SMLU_ERR_ARG, "op must be SMLU_OP_N, SMLU_OP_T or SMLU_OP_H");
+  if (max_steps < -1) return fail(h, SMLU_ERR_ARG, "max_steps must be -1 (the handle's rule), 0 or a step limit");
+  if (!h->have_numeric || h->errcol >= 0)
+    return fail(h, SMLU_ERR_STATE, "no numeric factorization (none yet, or a singular one)");
+  if (h->nranks > 1) return fail(h, SMLU_ERR_STATE, "batched refinement is single-GPU only");
+  const int64_t n = h->plan.n;
+  if (ldb < n || ldx < n) return fail(h, SMLU_ERR_ARG, "leading dimension smaller than n");
+  *conj = h->zc && op == SMLU_OP_T;
+  *steps = max_steps < 0 ? auto_refine_steps(h) : max_steps;
+  return SMLU_OK;
+}
+
+int smlu_solve_refined_multi_device(smlu_handle* h, int op, int max_steps, int64_t nrhs, const double* d_B,
+                                    int64_t ldb, double* d_X, int64_t ldx, smlu_refine_info* info) {
+  int conj = 0, steps = 0;
+  int rc = refined_multi_check(h, op, max_steps, nrhs, d_B, ldb, d_X, ldx, &conj, &steps);
+  if (rc != SMLU_OK || nrhs == 0) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(after_caller(h));
+  return solve_refined_multi_dev(h, op, conj, steps, nrhs, d_B, ldb, d_X, ldx, info);
+}
+
+int smlu_solve_refined_multi(smlu_handle* h, int op, int max_steps, int64_t nrhs, const double* B, int64_t ldb,
+                             double* X, int64_t ldx, smlu_refine_info* info) {
+  int conj = 0, steps = 0;
+  int rc = refined_multi_check(h, op, max_steps, nrhs, B, ldb, X, ldx, &conj, &steps);
+  if (rc != SMLU_OK || nrhs == 0) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  const int64_t n = h->plan.n;
+  if (!h->wrk2m.p) HIPCHK(h->wrk2m.alloc((size_t)n * kMultiRhs));   // batches staged as in smlu_solve_multi
+  double* d = h->wrk2m.p;
+  int max_steps_seen = 0;
+  double max_berr = -1, max_resid = -1, ms = 0;
+  for (int64_t j = 0; j < nrhs; j += kMultiRhs) {
+    const int64_t nb = std::min<int64_t>(kMultiRhs, nrhs - j);
+    HIPCHK(hipMemcpy2DAsync(d, sizeof(double) * n, B + j * ldb, sizeof(double) * ldb, sizeof(double) * n, nb,
+                            hipMemcpyHostToDevice, h->stream));
+    rc = solve_refined_multi_dev(h, op, conj, steps, nb, d, n, d, n, info ? info + j : nullptr);
+    if (rc != SMLU_OK) return rc;
+    max_steps_seen = std::max(max_steps_seen, h->refine_steps);
+    max_berr = std::max(max_berr, h->refine_berr);
+    max_resid = std::max(max_resid, h->refine_resid);
+    ms += h->solve_ms;
+    HIPCHK(hipMemcpy2DAsync(X + j * ldx, sizeof(double) * ldx, d, sizeof(double) * n, sizeof(double) * n, nb,
+                            hipMemcpyDeviceToHost, h->stream));
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->refine_steps = max_steps_seen;
+  h->refine_berr = max_berr;
+  h->refine_resid = max_resid;
+  h->solve_ms = ms;
+  return SMLU_OK;
+}
+
 static int tri_solve_host(smlu_handle* h, double* x, int mode) {
   if (!h || !x) return fail(h, SMLU_ERR_ARG, "NULL argument");
   if (!h->have_numeric) return fail(h, SMLU_ERR_STATE, "no numeric factorization");

@@ -3,7 +3,7 @@
 # its argument count).  See INTEGRATION.md.
 module SharedMemSparseLU
 
-export ParallelSparseLU, cleanup_ParallelSparseLU!, allocate_shared, gmres!
+export ParallelSparseLU, cleanup_ParallelSparseLU!, allocate_shared, gmres!, ldiv_refined!
 
 using LinearAlgebra, SparseArrays, Libdl
 import LinearAlgebra: ldiv!, lu!
@@ -185,6 +185,36 @@ function _ldiv_trans!(op::Int32, x::AbstractVecOrMat, F::ParallelSparseLU{Tf}, b
 end
 ldiv!(x::AbstractVecOrMat, W::TransposedLU, b::AbstractVecOrMat) = _ldiv_trans!(Int32(1), x, W.parent, b)
 ldiv!(x::AbstractVecOrMat, W::AdjointLU, b::AbstractVecOrMat) = _ldiv_trans!(Int32(2), x, W.parent, b)
+
+# ldiv_refined!(X, F, B; steps=-1), also on transpose(F) and F': the columns of B solved with iterative
+# refinement run as a batch (smlu_solve_refined_multi): up to 16 columns share every pass over the
+# factors and every residual pass over A, each column is refined by the rule of the single solve and
+# is bitwise ldiv!(x, F, b) of that column.  steps = -1: the handle's own rule; 0: a plain batch;
+# k > 0: up to k corrections per column.  Returns (steps, berr), one entry per column: the corrections
+# applied and the last componentwise backward error measured (-1 when nothing was refined).
+# RefineInfo must match the header's refinement record field for field.
+struct RefineInfo; steps::Int32; stop::Int32; berr::Float64; resid::Float64; end
+function _ldiv_refined!(op::Int32, X::AbstractMatrix, F::ParallelSparseLU{Tf}, B::AbstractMatrix, steps::Integer) where {Tf}
+    F.m == F.n || throw(DimensionMismatch("`F` is not square: F.m=$(F.m), F.n=$(F.n)"))
+    size(X) == size(B) || throw(DimensionMismatch("`X` has size $(size(X)), `B` has size $(size(B))"))
+    size(B, 1) == F.n || throw(DimensionMismatch("`B` does not have same size as F: size(B, 1)=$(size(B, 1)), F.n=$(F.n)"))
+    steps >= -1 || throw(ArgumentError("ldiv_refined!: steps must be -1, 0 or a step limit, got $steps"))
+    bb = B isa Array{Tf} ? B : Array{Tf}(B)
+    xx = X isa Array{Tf} ? X : similar(bb)
+    info = Vector{RefineInfo}(undef, size(B, 2))
+    ld = (Tf === ComplexF64 ? 2 : 1) * F.n      # leading dimension in doubles
+    check(ccall((:smlu_solve_refined_multi, libsmlu), Int32,
+                (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Tf}, Int64, Ptr{Tf}, Int64, Ptr{RefineInfo}),
+                F.handle, op, Int32(steps), size(B, 2), bb, ld, xx, ld, info), F.handle)
+    xx === X || copyto!(X, xx)
+    return [i.steps for i in info], [i.berr for i in info]
+end
+ldiv_refined!(X::AbstractMatrix, F::ParallelSparseLU, B::AbstractMatrix; steps::Integer=-1) =
+    _ldiv_refined!(Int32(0), X, F, B, steps)
+ldiv_refined!(X::AbstractMatrix, W::TransposedLU, B::AbstractMatrix; steps::Integer=-1) =
+    _ldiv_refined!(Int32(1), X, W.parent, B, steps)
+ldiv_refined!(X::AbstractMatrix, W::AdjointLU, B::AbstractMatrix; steps::Integer=-1) =
+    _ldiv_refined!(Int32(2), X, W.parent, B, steps)
 
 # logabsdet(F), logdet(F), det(F) and cond(F, p) from the factors on the GPU (smlu_logabsdet*,
 # smlu_rcond): no factor download.  The sign of a ComplexF64 factorization is its phase.

@@ -71,6 +71,11 @@ class SmluGmresInfo(ctypes.Structure):
                 ("relres", f64), ("relres_est", f64), ("berr", f64), ("bnorm", f64)]
 
 
+class SmluRefineInfo(ctypes.Structure):
+    """smlu_refine_info: one column of smlu_solve_refined_multi*."""
+    _fields_ = [("steps", i32), ("stop", i32), ("berr", f64), ("resid", f64)]
+
+
 # exported symbols and their signatures (restype, argtypes); the CPU test-suite checks that
 # every function declared in include/smlu.h is present here and in the .so
 SIGNATURES = {
@@ -95,6 +100,8 @@ SIGNATURES = {
     "smlu_solve_trans_device": (i32, [vp, i32, vp, vp]),
     "smlu_solve_trans_multi": (i32, [vp, i32, i64, vp, i64, vp, i64]),
     "smlu_solve_trans_multi_device": (i32, [vp, i32, i64, vp, i64, vp, i64]),
+    "smlu_solve_refined_multi": (i32, [vp, i32, i32, i64, vp, i64, vp, i64, ctypes.POINTER(SmluRefineInfo)]),
+    "smlu_solve_refined_multi_device": (i32, [vp, i32, i32, i64, vp, i64, vp, i64, ctypes.POINTER(SmluRefineInfo)]),
     "smlu_logabsdet": (i32, [vp, f64p, f64p]),
     "smlu_logabsdet_z": (i32, [vp, f64p, f64p]),
     "smlu_rcond": (i32, [vp, i32, f64p, f64p, f64p]),

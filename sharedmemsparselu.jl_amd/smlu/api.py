@@ -7,6 +7,7 @@ lu!(F, A)                           lu_(F, A)                     :245-279
 ldiv!(x, F, b)                      ldiv_(x, F, b)                :286-342
 ldiv!(x, transpose(F), b)           ldiv_(x, F, b, trans="T")     (not in the reference)
 ldiv!(x, F', b)                     ldiv_(x, F, b, trans="C")     (not in the reference)
+ldiv_refined!(X, F, B)              ldiv_refined_(X, F, B)        (not in the reference)
 lsolve!(F, x), rsolve!(F, x)        lsolve_(F, x), rsolve_(F, x)  :349-392
 logabsdet(F), det(F), logdet(F)     F.logabsdet() F.det() F.logdet()  (not in the reference)
 cond(F, 1), cond(F, Inf)            F.condest("1"|"inf"), F.rcond()   (not in the reference)
@@ -122,6 +123,24 @@ def _device_f64(name, t, size):
 def _gmres_info(rc, ci):
     return GmresInfo(bool(ci.converged), ci.iters, ci.cycles, ci.solves, ci.relres, ci.relres_est, ci.berr,
                      ci.bnorm, rc)
+
+
+def _refine_steps(steps):
+    """steps=None -> -1 (the handle's rule); otherwise an integer >= 0 (max_steps of
+    smlu_solve_refined_multi*)."""
+    if steps is None:
+        return -1
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 0:
+        raise ValueError(f"steps must be None or an integer >= 0, got {steps!r}")
+    return int(steps)
+
+
+def _refine_info(info, nrhs):
+    """The smlu_refine_info array of a call as a dict of per-column numpy arrays."""
+    return dict(steps=np.array([info[j].steps for j in range(nrhs)], np.int32),
+                stop=np.array([info[j].stop for j in range(nrhs)], np.int32),
+                berr=np.array([info[j].berr for j in range(nrhs)], np.float64),
+                resid=np.array([info[j].resid for j in range(nrhs)], np.float64))
 
 
 def _check(rc, h=None):
@@ -376,6 +395,27 @@ class ParallelSparseLU:
             return _check(C.lib().smlu_solve_multi_device(self._h, nrhs, ctypes.c_void_p(d_B.data_ptr()), ld,
                                                           ctypes.c_void_p(d_X.data_ptr()), ld), self._h)
 
+    def solve_refined_multi_device(self, d_X, d_B, trans="N", steps=None):
+        """ldiv! for several right-hand sides with iterative refinement run as a batch
+        (smlu_solve_refined_multi_device): d_B, d_X are (nrhs, n) contiguous torch tensors as in
+        solve_multi_device.  Up to 16 columns share each solve pass and each residual pass; every
+        column is refined by the rule of the single solve and is bitwise solve_device(...,
+        trans=...) of that column alone.  steps=None: the handle's own rule; 0: a plain batch;
+        k > 0: up to k corrections per column.  Returns a dict of per-column arrays: steps and stop
+        (int32; stop 0 not refined, 1 berr <= 2^-51, 2 berr did not halve, 3 step limit), berr and
+        resid (float64, the last ones measured; -1 when nothing was refined)."""
+        op = _op(trans)
+        nrhs, n = d_B.shape
+        if n != self.n or tuple(d_X.shape) != (nrhs, n):
+            raise DimensionMismatch(f"B has shape {tuple(d_B.shape)}, X has shape {tuple(d_X.shape)}, n={self.n}")
+        ld = 2 * n if self.is_complex else n     # leading dimension in doubles
+        info = (C.SmluRefineInfo * max(nrhs, 1))()
+        with C.caller_stream(self._h, d_B):
+            _check(C.lib().smlu_solve_refined_multi_device(
+                self._h, op, _refine_steps(steps), nrhs, ctypes.c_void_p(d_B.data_ptr()), ld,
+                ctypes.c_void_p(d_X.data_ptr()), ld, info), self._h)
+        return _refine_info(info, nrhs)
+
     # ---- determinant and condition estimate (smlu_logabsdet*, smlu_rcond) ----
     def logabsdet(self):
         """(log|det A|, sign) of the current factorization, as Julia's logabsdet(F): sign is +1.0 or
@@ -567,6 +607,33 @@ def ldiv_(x, F: ParallelSparseLU, b, trans="N"):
     if xx is not x:
         x[:] = xx
     return x
+
+
+def ldiv_refined_(X, F: ParallelSparseLU, B, trans="N", steps=None):
+    """ldiv!(X, F, B) for 2D ``X`` / ``B`` (columns) with iterative refinement run as a batch
+    (smlu_solve_refined_multi): up to 16 columns share every pass, each column is refined by the rule
+    of the single solve and is bitwise ``ldiv_(x, F, b, trans)`` of that column.  ``X is B`` is
+    allowed.  steps as in ParallelSparseLU.solve_refined_multi_device, whose dict it returns."""
+    op = _op(trans)
+    if np.ndim(B) != 2 or np.shape(X) != np.shape(B):
+        raise DimensionMismatch(f"`X` has size {np.shape(X)}, `B` has size {np.shape(B)}: two equal 2D arrays")
+    if np.shape(B)[0] != F.n:
+        raise DimensionMismatch(f"`B` does not have same size as F: size(B, 1)={np.shape(B)[0]}, F.n={F.n}")
+    if not F.is_complex and (np.iscomplexobj(B) or np.iscomplexobj(X)):
+        raise TypeError("complex vectors need a factorization of a complex matrix")
+    _need_complex_x(F, X)
+    nrhs = np.shape(B)[1]
+    dt = F._dt
+    bb = np.asfortranarray(B, dtype=dt)
+    xx = X if (isinstance(X, np.ndarray) and X.dtype == dt and X.flags.f_contiguous) \
+        else np.empty((F.n, nrhs), dtype=dt, order="F")
+    ld = 2 * F.n if F.is_complex else F.n   # leading dimension in doubles
+    info = (C.SmluRefineInfo * max(nrhs, 1))()
+    _check(C.lib().smlu_solve_refined_multi(F._h, op, _refine_steps(steps), nrhs, C.ptr(bb), ld, C.ptr(xx), ld, info),
+           F._h)
+    if xx is not X:
+        X[:, :] = xx
+    return _refine_info(info, nrhs)
 
 
 def _need_complex_x(F, x):
