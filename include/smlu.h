@@ -394,7 +394,8 @@ void smlu_destroy(smlu_handle* h);
 
 /* Diagnostics. */
 const char* smlu_last_error_string(const smlu_handle* h);   /* h may be NULL: thread-global */
-int64_t     smlu_last_error_col(const smlu_handle* h);      /* column of a zero/weak pivot, 0-based, -1 none */
+int64_t     smlu_last_error_col(const smlu_handle* h);      /* column of A (the caller's numbering, but 0-based
+                                                               whatever index_base is) whose pivot was zero; -1 none */
 
 /* Plan statistics (host symbolic analysis): keys are
  * "n","nnzA","nsuper","nlevels","nnzL","nnzU","nnzLU","flops","upd","front_max","ns_max",

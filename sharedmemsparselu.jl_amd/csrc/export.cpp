@@ -292,6 +292,7 @@ int smlu_create_with_pivots(int64_t n, const int64_t* colptr, const int64_t* row
                             const double* Rs, const int64_t* Lcolptr, const int64_t* Lrowval,
                             const int64_t* Ucolptr, const int64_t* Urowval, const smlu_opts* opts,
                             smlu_handle** out) {
+  if (out) *out = nullptr;   // no handle on any refusal below
   if (!p || !q) return fail(nullptr, SMLU_ERR_ARG, "p and q are required");
   const bool pat = Lcolptr || Lrowval || Ucolptr || Urowval;
   std::vector<int64_t> Lp, Li, Up, Ui;

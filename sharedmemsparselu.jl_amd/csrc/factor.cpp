@@ -506,6 +506,7 @@ int refactor_csc_impl(smlu_handle* h, int64_t n, const int64_t* colptr, const in
   for (int64_t j = 0; same && j <= n; ++j) same = (colptr[j] - base == P.Acolptr[j]);
   for (int64_t e = 0; same && e < P.nnzA; ++e) same = (rowval[e] - base == P.Arow[e]);
   if (same) return smlu_refactor(h, nzval);
+  if (colptr[0] != base) return fail(h, SMLU_ERR_ARG, "colptr[0] must equal index_base");   // handle untouched
   // pattern changed: the reference re-chunks and re-allocates (src/SharedMemSparseLU.jl:265-273);
   // here: re-analysis and re-allocation in place, keeping the options and the stream.
   h->release_buffers();

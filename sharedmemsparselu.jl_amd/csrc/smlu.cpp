@@ -68,6 +68,8 @@ int create_impl(int64_t n, const int64_t* colptr, const int64_t* rowval, const d
   if (opts) h->opts = *opts;
   else smlu_default_opts(&h->opts);
   if (!valid_opts(&h->opts)) return fail(nullptr, SMLU_ERR_ARG, "index_base must be 0 or 1");
+  // before anything indexes rowval / nzval with colptr[j] - base (a 0-based colptr under base 1)
+  if (colptr[0] != h->opts.index_base) return fail(nullptr, SMLU_ERR_ARG, "colptr[0] must equal index_base");
   if (h->opts.chunk_size <= 0 || h->opts.chunk_size > n) h->opts.chunk_size = std::min<int64_t>(8, n);
   int rc = check_device(h.get());
   if (rc != SMLU_OK) return rc;
@@ -160,7 +162,10 @@ const char* smlu_last_error_string(const smlu_handle* h) {
 
 int64_t smlu_last_error_col(const smlu_handle* h) {
   if (!h) return -1;
-  return (h->zc && h->errcol >= 0) ? h->errcol / 2 : h->errcol;   // complex handle: column of A
+  // errcol is a pivot position: the caller's column is q[position] (complex handle: K's column / 2)
+  if (h->errcol < 0 || h->errcol >= (int64_t)h->plan.q.size()) return h->errcol < 0 ? -1 : h->errcol;
+  const int64_t col = h->plan.q[h->errcol];
+  return h->zc ? col / 2 : col;
 }
 
 static double plan_stat(const Plan& P, const std::string& k) {

@@ -156,12 +156,16 @@ class ParallelSparseLU:
 
     ``F.L * F.U == (F.Rs[:, None] * A)[F.p][:, F.q]`` (UMFPACK's relation quoted at
     src/SharedMemSparseLU.jl:305-316), with 0-based ``p``/``q``.
+
+    ``scale=False``: no row scaling (``smlu_opts.scale = 0``, ``F.Rs`` all ones).  ``index_base=1``:
+    the index arrays cross the C ABI 1-based, as the Julia shim passes them; everything on the
+    Python side stays 0-based.
     """
 
     def __init__(self, A, chunk_size=None, *, ordering="auto", grid=None, device=0,
                  profile=False, p=None, q=None, Rs=None, pivot_tol=None, diag_pivot_tol=None,
                  leaf_size=None, relax=True, use_mfma=None, refine=None,
-                 int32_indices=False, L_pattern=None, U_pattern=None):
+                 int32_indices=False, L_pattern=None, U_pattern=None, scale=True, index_base=0):
         A = _csc(A)
         m, n = A.shape
         if m != n:
@@ -171,8 +175,13 @@ class ParallelSparseLU:
         chunk_size = min(int(chunk_size), n)     # :72
         order = {"auto": C.ORDER_AUTO, "natural": C.ORDER_NATURAL, "nd": C.ORDER_GRAPH_ND,
                  "geometric": C.ORDER_GEOMETRIC_ND, "amd": C.ORDER_AMD, "given": C.ORDER_GIVEN}[ordering]
-        kw = dict(chunk_size=chunk_size, index_base=0, ordering=order, device=device,
-                  profile=1 if profile else 0, relax=1 if relax else 0)
+        if index_base not in (0, 1):
+            raise ValueError(f"index_base must be 0 or 1, got {index_base!r}")
+        # index_base=1: the index arrays cross the C-ABI 1-based, as Julia passes them; this class
+        # stays 0-based on its Python side (arguments and F.L / F.U / F.p / F.q)
+        base = self._base = int(index_base)
+        kw = dict(chunk_size=chunk_size, index_base=base, ordering=order, device=device,
+                  profile=1 if profile else 0, relax=1 if relax else 0, scale=1 if scale else 0)
         if grid is not None:
             kw["grid"] = grid
             if ordering == "auto":
@@ -197,14 +206,15 @@ class ParallelSparseLU:
         vals = np.ascontiguousarray(A.data, dtype=self._dt)
         h = ctypes.c_void_p()
         L = C.lib()
+        colptr, rowval = self._colptr + base, self._rowval + base
         if self.is_complex:
             if p is not None or q is not None or int32_indices:
                 raise ValueError("complex matrices take neither a given (p, q) nor Int32 indices")
-            rc = L.smlu_create_z(n, C.ptr(self._colptr), C.ptr(self._rowval), C.ptr(vals),
+            rc = L.smlu_create_z(n, C.ptr(colptr), C.ptr(rowval), C.ptr(vals),
                                  ctypes.byref(self._opts), ctypes.byref(h))
         elif p is not None or q is not None:
-            pp = np.ascontiguousarray(p, dtype=np.int64)
-            qq = np.ascontiguousarray(q, dtype=np.int64)
+            pp = np.ascontiguousarray(p, dtype=np.int64) + base
+            qq = np.ascontiguousarray(q, dtype=np.int64) + base
             rs = None if Rs is None else np.ascontiguousarray(Rs, dtype=np.float64)
             # UMFPACK's F.L / F.U patterns: any sparse matrix, only the pattern is used
             pat = []
@@ -214,19 +224,19 @@ class ParallelSparseLU:
                 else:
                     M = sp.csc_matrix(M)
                     M.sort_indices()
-                    pat += [np.ascontiguousarray(M.indptr, dtype=np.int64),
-                            np.ascontiguousarray(M.indices, dtype=np.int64)]
-            rc = L.smlu_create_with_pivots(n, C.ptr(self._colptr), C.ptr(self._rowval), C.ptr(vals),
+                    pat += [np.ascontiguousarray(M.indptr, dtype=np.int64) + base,
+                            np.ascontiguousarray(M.indices, dtype=np.int64) + base]
+            rc = L.smlu_create_with_pivots(n, C.ptr(colptr), C.ptr(rowval), C.ptr(vals),
                                            C.ptr(pp), C.ptr(qq), C.ptr(rs), *[C.ptr(a) for a in pat],
                                            ctypes.byref(self._opts), ctypes.byref(h))
         elif int32_indices:
             # SparseMatrixCSC{Float64,Int32}: the Int32 entry point
-            cp32 = np.ascontiguousarray(A.indptr, dtype=np.int32)
-            ri32 = np.ascontiguousarray(A.indices, dtype=np.int32)
+            cp32 = np.ascontiguousarray(A.indptr, dtype=np.int32) + np.int32(base)
+            ri32 = np.ascontiguousarray(A.indices, dtype=np.int32) + np.int32(base)
             rc = L.smlu_create_i32(n, C.ptr(cp32), C.ptr(ri32), C.ptr(vals),
                                    ctypes.byref(self._opts), ctypes.byref(h))
         else:
-            rc = L.smlu_create(n, C.ptr(self._colptr), C.ptr(self._rowval), C.ptr(vals),
+            rc = L.smlu_create(n, C.ptr(colptr), C.ptr(rowval), C.ptr(vals),
                                ctypes.byref(self._opts), ctypes.byref(h))
         if rc < 0:
             raise SmluError(f"smlu_create failed ({rc}): {C.last_error(None)}")
@@ -253,8 +263,9 @@ class ParallelSparseLU:
             p = np.empty(n, np.int64); q = np.empty(n, np.int64); Rs = np.empty(n)
             _check(L.smlu_get_factors_z(self._h, C.ptr(Lp), C.ptr(Li), C.ptr(Lx), C.ptr(Up), C.ptr(Ui),
                                         C.ptr(Ux), C.ptr(p), C.ptr(q), C.ptr(Rs)), self._h)
-            self._zfactors = dict(L=sp.csc_matrix((Lx, Li, Lp), shape=(n, n)),
-                                  U=sp.csc_matrix((Ux, Ui, Up), shape=(n, n)), p=p, q=q, Rs=Rs)
+            b = self._base
+            self._zfactors = dict(L=sp.csc_matrix((Lx, Li - b, Lp - b), shape=(n, n)),
+                                  U=sp.csc_matrix((Ux, Ui - b, Up - b), shape=(n, n)), p=p - b, q=q - b, Rs=Rs)
         return self._zfactors
 
     def real_equivalent_factors(self):
@@ -269,8 +280,9 @@ class ParallelSparseLU:
             p = np.empty(n, np.int64); q = np.empty(n, np.int64); Rs = np.empty(n)
             _check(L.smlu_get_factors(self._h, C.ptr(Lp), C.ptr(Li), C.ptr(Lx), C.ptr(Up), C.ptr(Ui),
                                       C.ptr(Ux), C.ptr(p), C.ptr(q), C.ptr(Rs)), self._h)
-            self._factors = dict(L=sp.csc_matrix((Lx, Li, Lp), shape=(n, n)),
-                                 U=sp.csc_matrix((Ux, Ui, Up), shape=(n, n)), p=p, q=q, Rs=Rs)
+            b = self._base
+            self._factors = dict(L=sp.csc_matrix((Lx, Li - b, Lp - b), shape=(n, n)),
+                                 U=sp.csc_matrix((Ux, Ui - b, Up - b), shape=(n, n)), p=p - b, q=q - b, Rs=Rs)
         return self._factors
 
     @property
@@ -303,7 +315,7 @@ class ParallelSparseLU:
         p = np.empty(n, np.int64); q = np.empty(n, np.int64); Rs = np.empty(n)
         _check(C.lib().smlu_get_factors(self._h, None, None, None, None, None, None, C.ptr(p), C.ptr(q),
                                         C.ptr(Rs)), self._h)
-        return p, q, Rs
+        return p - self._base, q - self._base, Rs
 
     def front_store(self):
         """Diagnostics (smlu_dev_front_offsets / smlu_dev_copy): the factor store as one host array
@@ -555,7 +567,8 @@ def lu_(F: ParallelSparseLU, A):
         F._colptr = np.ascontiguousarray(A.indptr, dtype=np.int64)
         F._rowval = np.ascontiguousarray(A.indices, dtype=np.int64)
         fn = L.smlu_refactor_csc_z if F.is_complex else L.smlu_refactor_csc
-        rc = fn(F._h, F.n, C.ptr(F._colptr), C.ptr(F._rowval), C.ptr(vals))
+        colptr, rowval = F._colptr + F._base, F._rowval + F._base
+        rc = fn(F._h, F.n, C.ptr(colptr), C.ptr(rowval), C.ptr(vals))
     F._factors = None
     F._zfactors = None
     _check(rc, F._h)

@@ -46,13 +46,17 @@ def pivot_parity(A, F, prev_pivmode=0, full_piv_ns=None, given=False):
     return p_or
 
 
-def factor_parity(A, F, rtol=1e-12, prev_pivmode=0, full_piv_ns=None):
+def factor_parity(A, F, rtol=1e-12, prev_pivmode=0, full_piv_ns=None, Rs_ref=None):
     """Pivot order chosen independently by the multifrontal oracle (pivot_parity), then the
-    exported factors vs the oracle's fixed-pivot LU of (Rs.*A)[p, q]."""
-    pivot_parity(A, F, prev_pivmode=prev_pivmode, full_piv_ns=full_piv_ns)
+    exported factors vs the oracle's fixed-pivot LU of (Rs.*A)[p, q].  Rs_ref: the row scaling the
+    handle must hold bitwise (default: UMFPACK's SUM scaling, O.rowscale(A)); with another one (a
+    handle created with scale=False holds all ones) the multifrontal oracle, which restates
+    pivoting only under SUM scaling, is left out and the fixed-pivot oracle runs on the handle's own p."""
+    if Rs_ref is None:
+        pivot_parity(A, F, prev_pivmode=prev_pivmode, full_piv_ns=full_piv_ns)
     fx = _real(F)
     p, q, Rs = fx["p"], fx["q"], fx["Rs"]
-    Ro = O.rowscale(A)
+    Ro = O.rowscale(A) if Rs_ref is None else np.ascontiguousarray(Rs_ref, dtype=np.float64)
     assert np.array_equal(Rs, Ro), "row scaling must be bitwise identical"
     ref = O.OracleLU(A, p, q, Ro)
     assert ref.status == 0
@@ -90,19 +94,24 @@ def tile_pivoting_matrix(n, seed):
     return D
 
 
-def front_parity(A, F, rtol=1e-12, threads=16, prev_pivmode=0):
+def front_parity(A, F, rtol=1e-12, threads=16, prev_pivmode=0, Rs_ref=None):
     """Factor parity at sizes the one-core fixed-pivot oracle cannot reach: the multifrontal oracle
     (oracle/mf.c, OpenMP) chooses its own pivots on the handle's assembly tree (the candidate modes
     and the re-pivoting decision restated as in pivot_parity: modes, pivmode and p bit-identical,
     Rs bitwise), then EVERY front's stored factor values -- its L panel (M x ns: unit-lower
     multipliers and U11) and U12 (ns x nu) -- are compared entry by entry with the GPU's factor
     store (smlu_dev_front_offsets / smlu_dev_copy).  Tolerance per front: rtol * growth * max(1,
-    max |front|).  Returns (fronts compared, entries compared, worst scaled difference)."""
+    max |front|).  Returns (fronts compared, entries compared, worst scaled difference).
+    Rs_ref: the row scaling the handle must hold bitwise when it is not O.rowscale(A).  The oracle
+    always assembles the SUM-scaled entries rowscale(A)[row] * a, so with Rs_ref the handle must be
+    one that assembles the same products: a scale=False handle (Rs_ref all ones) of the matrix
+    whose entries are those products, with A still the unscaled matrix."""
     A = sp.csc_matrix(A)
     A.sort_indices()
     fr = F.fronts()
     p, q, Rs = F.perm_scale()
-    assert np.array_equal(Rs, O.rowscale(A)), "row scaling must be bitwise identical"
+    assert np.array_equal(Rs, O.rowscale(A) if Rs_ref is None else Rs_ref), "row scaling must be bitwise identical"
+    Rs = O.rowscale(A)
     p_or, pm, modes, _, mf = O.gpu_pivot_choice(A, q, fr, pivmode=prev_pivmode, pivot_tol=F.stat("pivot_tol"),
                                                 diag_tol=F.stat("diag_pivot_tol"), threads=threads, keep=True)
     try:
