@@ -146,7 +146,8 @@ int smlu_residual_device(smlu_handle* h, const double* d_x, const double* d_b, d
  * host memory, X == B allowed.  The reference's ldiv! is generic over the vector type
  * (src/SharedMemSparseLU.jl:286); multiple RHS are SURVEY §8f-4.  "solve_passes" counts the forward
  * solve passes run on the handle so far, refinement corrections included: one per single-vector
- * solve, one per batch of up to 16 columns (the forward twin of "solve_trans_passes"). */
+ * solve, one per batch of up to 16 columns (the forward twin of "solve_trans_passes").
+ * "solve_ms_last" after a call is the sum over the batches (columns) it ran. */
 int smlu_solve_multi(smlu_handle* h, int64_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx);
 
 /* Same with device pointers. */

@@ -1,5 +1,5 @@
 // kernels_common.hpp — device helpers shared by the gfx950 kernel translation units
-// (kernels_front.hip, kernels_gemm.hip, kernels_solve.hip).
+// (kernels_front.hip, kernels_gemm.hip, kernels_solve.hip), and the launch helpers of their wrappers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -282,5 +282,31 @@ __device__ __forceinline__ double dot64(const double* __restrict__ D, int64_t M,
     if (j < bw) acc = fma(d[j], xs[j], acc);
   return acc;
 }
+
+// ---- host-side launch helpers ---------------------------------------------------------------
+static inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
+static inline bool bad_rhs(Rhs rh) { return rh.n < 1 || rh.n > kMultiRhs; }
+
+// The body of a solve launch wrapper (solve.cpp's run_solve_launch / run_solve_launch_t; st and rh
+// are the wrapper's stream and Rhs): launches K<NR> / K<FLAG, NR> with (args..., rh) at the smallest
+// width NR of 1, 4, 8, 16 that holds rh.n columns, and returns.
+#define SMLU_BY_WIDTH(K, GRID, BLOCK, ...)                                     \
+  do {                                                                         \
+    if (bad_rhs(rh)) return hipErrorInvalidValue;                              \
+    if (rh.n == 1) K<1><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);           \
+    else if (rh.n <= 4) K<4><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);      \
+    else if (rh.n <= 8) K<8><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);      \
+    else K<16><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);                    \
+    return hipGetLastError();                                                  \
+  } while (0)
+#define SMLU_BY_WIDTH2(K, FLAG, GRID, BLOCK, ...)                                    \
+  do {                                                                               \
+    if (bad_rhs(rh)) return hipErrorInvalidValue;                                    \
+    if (rh.n == 1) K<FLAG, 1><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);           \
+    else if (rh.n <= 4) K<FLAG, 4><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);      \
+    else if (rh.n <= 8) K<FLAG, 8><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);      \
+    else K<FLAG, 16><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);                    \
+    return hipGetLastError();                                                        \
+  } while (0)
 
 }  // namespace smlu

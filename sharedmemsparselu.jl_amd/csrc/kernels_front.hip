@@ -1693,7 +1693,6 @@ __global__ __launch_bounds__(256) void k_step_trsm(const FrontTile* __restrict__
 // ------------------------------------------------------------------------------------
 // Host-side launch wrappers (called from smlu.cpp)
 // ------------------------------------------------------------------------------------
-static inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
 // Dynamic LDS above 64 KiB must be enabled per kernel before launch (and before any capture).
 hipError_t init_kernel_attributes() {

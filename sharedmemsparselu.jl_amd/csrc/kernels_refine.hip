@@ -147,7 +147,7 @@ __global__ void k_refine_record(const double* __restrict__ nrm, long long* __res
 }
 
 // ---- host-side launch wrappers (solve.cpp) ---------------------------------------------------
-// The width is the smallest of 1, 4, 8, 16 that holds the active columns (SMLU_T's rule).
+// The width is the smallest of 1, 4, 8, 16 that holds the active columns (SMLU_BY_WIDTH's rule).
 #define SMLU_R(K, ...)                                                          \
   do {                                                                          \
     const unsigned g = (unsigned)((n + 255) / 256);                             \

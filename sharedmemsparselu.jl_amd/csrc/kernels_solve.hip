@@ -50,7 +50,6 @@ __device__ __forceinline__ double tri_lds(double xi, const double* __restrict__ 
 // value loaded from HBM is applied to all right-hand sides; read-modify-writes of the front
 // vectors load all right-hand sides before the first store.  With NR == 1 the arithmetic and its
 // order are those of the single-vector solve.
-constexpr int kMaxRhs = kMultiRhs;
 
 // st(r, i, ld(r, i)) for r < nr, i < cnt, strided over the workgroup's nthr threads, four
 // (r, i) pairs per thread and round: the four loads are issued before the first store (the
@@ -671,7 +670,7 @@ __device__ __forceinline__ void atomic_write_f64(double* p, double v) {
                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // Bounded wait for flag f to reach the epoch.  A wait that gives up raises *status; the host reads
-// it after every solve and re-runs the solve on the per-block schedule (smlu.cpp: run_solve_dev), so
+// it after every solve and re-runs the solve on the per-block schedule (solve.cpp: run_solve_dev), so
 // a timed-out chunk's values are never returned.  spin <= 0 reports every wait as timed out (the
 // tests' forced-fallback knob SMLU_SWEEP_SPIN=0).
 __device__ __forceinline__ void sweep_wait(int32_t* f, int32_t epoch, int32_t* status, int spin) {
@@ -1219,35 +1218,25 @@ __global__ void k_expand_z(int64_t nnz, const double2* __restrict__ z, const int
 }
 
 // ------------------------------------------------------------------------------------
-// Host-side launch wrappers (called from smlu.cpp)
+// Host-side launch wrappers (called from solve.cpp).  The instance of the batch width: SMLU_BY_WIDTH
+// (kernels_common.hpp) where a kernel has the four widths at one block size, written out otherwise.
 // ------------------------------------------------------------------------------------
-static inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 hipError_t launch_fwd(hipStream_t st, int cnt, const int32_t* list, const SNode* sn,
                       const int32_t* chlist, const int32_t* relmap, const int32_t* rowperm,
                       const double* store, double* x, double* vbuf, Rhs rh) {
   if (cnt <= 0) return hipSuccess;
-  if (rh.n < 1 || rh.n > kMaxRhs) return hipErrorInvalidValue;
-  if (rh.n == 1) k_fwd_front<1><<<cnt, 256, 0, st>>>(list, sn, chlist, relmap, rowperm, store, x, vbuf, rh);
-  else if (rh.n <= 4) k_fwd_front<4><<<cnt, 256, 0, st>>>(list, sn, chlist, relmap, rowperm, store, x, vbuf, rh);
-  else if (rh.n <= 8) k_fwd_front<8><<<cnt, 256, 0, st>>>(list, sn, chlist, relmap, rowperm, store, x, vbuf, rh);
-  else k_fwd_front<16><<<cnt, 256, 0, st>>>(list, sn, chlist, relmap, rowperm, store, x, vbuf, rh);
-  return hipGetLastError();
+  SMLU_BY_WIDTH(k_fwd_front, cnt, 256, list, sn, chlist, relmap, rowperm, store, x, vbuf);
 }
 hipError_t launch_bwd(hipStream_t st, int cnt, const int32_t* list, const SNode* sn,
                       const int32_t* rows, const double* store, double* x, double* vbuf, Rhs rh) {
   if (cnt <= 0) return hipSuccess;
-  if (rh.n < 1 || rh.n > kMaxRhs) return hipErrorInvalidValue;
-  if (rh.n == 1) k_bwd_front<1><<<cnt, 256, 0, st>>>(list, sn, rows, store, x, vbuf, rh);
-  else if (rh.n <= 4) k_bwd_front<4><<<cnt, 256, 0, st>>>(list, sn, rows, store, x, vbuf, rh);
-  else if (rh.n <= 8) k_bwd_front<8><<<cnt, 256, 0, st>>>(list, sn, rows, store, x, vbuf, rh);
-  else k_bwd_front<16><<<cnt, 256, 0, st>>>(list, sn, rows, store, x, vbuf, rh);
-  return hipGetLastError();
+  SMLU_BY_WIDTH(k_bwd_front, cnt, 256, list, sn, rows, store, x, vbuf);
 }
 hipError_t launch_fwd_tiny(hipStream_t st, int cnt, const int32_t* list, const SNode* sn,
                            const int32_t* chlist, const int32_t* relmap, const int32_t* rowperm,
                            const double* store, double* x, double* vbuf, Rhs rh, int micro) {
   if (cnt <= 0) return hipSuccess;
-  if (rh.n < 1 || rh.n > kMaxRhs) return hipErrorInvalidValue;
+  if (bad_rhs(rh)) return hipErrorInvalidValue;
   if (micro) {   // every front of the list has M <= 8 (batches too: the rows loaded once per front)
     k_fwd_micro<<<nblk(cnt, 32), 256, 0, st>>>(list, cnt, sn, chlist, relmap, rowperm, store, x, vbuf, rh);
     return hipGetLastError();
@@ -1255,13 +1244,13 @@ hipError_t launch_fwd_tiny(hipStream_t st, int cnt, const int32_t* list, const S
   const unsigned g = nblk(cnt, 4);
   if (rh.n == 1) k_fwd_tiny<1><<<g, 256, 0, st>>>(list, cnt, sn, chlist, relmap, rowperm, store, x, vbuf, rh);
   else if (rh.n <= 8) k_fwd_tiny<8><<<g, 256, 0, st>>>(list, cnt, sn, chlist, relmap, rowperm, store, x, vbuf, rh);
-  else k_fwd_tiny<kMaxRhs><<<g, 256, 0, st>>>(list, cnt, sn, chlist, relmap, rowperm, store, x, vbuf, rh);
+  else k_fwd_tiny<kMultiRhs><<<g, 256, 0, st>>>(list, cnt, sn, chlist, relmap, rowperm, store, x, vbuf, rh);
   return hipGetLastError();
 }
 hipError_t launch_bwd_tiny(hipStream_t st, int cnt, const int32_t* list, const SNode* sn,
                            const int32_t* rows, const double* store, double* x, double* vbuf, Rhs rh, int micro) {
   if (cnt <= 0) return hipSuccess;
-  if (rh.n < 1 || rh.n > kMaxRhs) return hipErrorInvalidValue;
+  if (bad_rhs(rh)) return hipErrorInvalidValue;
   if (micro) {
     k_bwd_micro<<<nblk(cnt, 32), 256, 0, st>>>(list, cnt, sn, rows, store, x, vbuf, rh);
     return hipGetLastError();
@@ -1271,33 +1260,27 @@ hipError_t launch_bwd_tiny(hipStream_t st, int cnt, const int32_t* list, const S
   // together (256 VGPRs)
   if (rh.n <= 4) k_bwd_tiny<4><<<g, 256, 0, st>>>(list, cnt, sn, rows, store, x, vbuf, rh);
   else if (rh.n <= 8) k_bwd_tiny<8><<<g, 256, 0, st>>>(list, cnt, sn, rows, store, x, vbuf, rh);
-  else k_bwd_tiny<kMaxRhs><<<g, 256, 0, st>>>(list, cnt, sn, rows, store, x, vbuf, rh);
+  else k_bwd_tiny<kMultiRhs><<<g, 256, 0, st>>>(list, cnt, sn, rows, store, x, vbuf, rh);
   return hipGetLastError();
 }
 hipError_t launch_fwd_pull(hipStream_t st, int64_t nwg, const FrontTile* ft, int nft, const SNode* sn,
                            const int32_t* rowperm, const int32_t* gptr, const int32_t* gent, const double* x,
                            double* vbuf, Rhs rh) {
   if (nwg <= 0) return hipSuccess;
-#define PULL(NR) k_fwd_pull<NR><<<(unsigned)nwg, 256, 0, st>>>(ft, nft, sn, rowperm, gptr, gent, x, vbuf, rh)
-  if (rh.n <= 1) PULL(1);
-  else if (rh.n <= 4) PULL(4);
-  else if (rh.n <= 8) PULL(8);
-  else PULL(16);
-#undef PULL
-  return hipGetLastError();
+  SMLU_BY_WIDTH(k_fwd_pull, (unsigned)nwg, 256, ft, nft, sn, rowperm, gptr, gent, x, vbuf);
 }
 hipError_t launch_fwd_gather(hipStream_t st, int cnt, const int32_t* list, const SNode* sn,
                              const int32_t* chlist, const int32_t* relmap, const int32_t* rowperm,
                              double* x, double* vbuf, Rhs rh) {
   if (cnt <= 0) return hipSuccess;
-  if (rh.n < 1 || rh.n > kMaxRhs) return hipErrorInvalidValue;
+  if (bad_rhs(rh)) return hipErrorInvalidValue;
   k_fwd_gather<<<dim3((unsigned)cnt, (unsigned)rh.n), 256, 0, st>>>(list, sn, chlist, relmap, rowperm, x, vbuf, rh);
   return hipGetLastError();
 }
 hipError_t launch_tri_block(hipStream_t st, bool upper, int64_t nwg, const FrontTile* ft, int nft,
                             int step, const SNode* sn, const double* store, double* x, double* vbuf, Rhs rh) {
   if (nwg <= 0) return hipSuccess;
-  if (rh.n < 1 || rh.n > kMaxRhs) return hipErrorInvalidValue;
+  if (bad_rhs(rh)) return hipErrorInvalidValue;
   // one chain wave for a single vector (320 threads), four for a batch (512)
 #define SMLU_TRI(NRV, THR)                                                                           \
   (upper ? (k_tri_block<true, NRV><<<(unsigned)nwg, THR, 0, st>>>(ft, nft, step, sn, store, x, vbuf, rh)) \
@@ -1312,13 +1295,8 @@ hipError_t launch_tri_block(hipStream_t st, bool upper, int64_t nwg, const Front
 hipError_t launch_bwd_u12(hipStream_t st, int64_t nwg, const FrontTile* ft, int nft, const SNode* sn,
                           const int32_t* rows, const double* store, const double* x, double* vbuf, Rhs rh) {
   if (nwg <= 0) return hipSuccess;
-  if (rh.n < 1 || rh.n > kMaxRhs) return hipErrorInvalidValue;
   // accumulators per right-hand side in registers: instantiate for the batch width
-  if (rh.n == 1) k_bwd_u12<1><<<(unsigned)nwg, 512, 0, st>>>(ft, nft, sn, rows, store, x, vbuf, rh);
-  else if (rh.n <= 4) k_bwd_u12<4><<<(unsigned)nwg, 512, 0, st>>>(ft, nft, sn, rows, store, x, vbuf, rh);
-  else if (rh.n <= 8) k_bwd_u12<8><<<(unsigned)nwg, 512, 0, st>>>(ft, nft, sn, rows, store, x, vbuf, rh);
-  else k_bwd_u12<16><<<(unsigned)nwg, 512, 0, st>>>(ft, nft, sn, rows, store, x, vbuf, rh);
-  return hipGetLastError();
+  SMLU_BY_WIDTH(k_bwd_u12, (unsigned)nwg, 512, ft, nft, sn, rows, store, x, vbuf);
 }
 hipError_t launch_tri_sweep(hipStream_t st, bool upper, int64_t nwg, const FrontTile* ft, int nft,
                             unsigned long long* tick, int32_t* flags, double* xh, int32_t* status, const SNode* sn,

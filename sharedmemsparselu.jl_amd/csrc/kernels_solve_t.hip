@@ -965,86 +965,62 @@ __global__ __launch_bounds__(256) void k_residual_t(int64_t n, const int64_t* __
 }
 
 // ---- host-side launch wrappers (solve.cpp) ---------------------------------------------------
-// The width is the smallest of 1, 4, 8, 16 that holds rh.n columns.  K<NR> / K<FLAG, NR>.
-#define SMLU_T(K, GRID, BLOCK, ...)                                            \
-  do {                                                                         \
-    if (bad_rhs(rh)) return hipErrorInvalidValue;                              \
-    if (rh.n == 1) K<1><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);           \
-    else if (rh.n <= 4) K<4><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);      \
-    else if (rh.n <= 8) K<8><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);      \
-    else K<16><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);                    \
-    return hipGetLastError();                                                  \
-  } while (0)
-#define SMLU_T2(K, FLAG, GRID, BLOCK, ...)                                           \
-  do {                                                                               \
-    if (bad_rhs(rh)) return hipErrorInvalidValue;                                    \
-    if (rh.n == 1) K<FLAG, 1><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);           \
-    else if (rh.n <= 4) K<FLAG, 4><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);      \
-    else if (rh.n <= 8) K<FLAG, 8><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);      \
-    else K<FLAG, 16><<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__, rh);                    \
-    return hipGetLastError();                                                        \
-  } while (0)
-
-static inline unsigned nblk_t(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
-static inline bool bad_rhs(Rhs rh) { return rh.n < 1 || rh.n > kMultiRhs; }
-
+// Every wrapper picks its instance with SMLU_BY_WIDTH (kernels_common.hpp).
 hipError_t launch_ut_tiny(hipStream_t st, int cnt, const int32_t* list, const SNode* sn, const int32_t* chlist,
                           const int32_t* relmap, const double* store, double* x, double* vbuf, Rhs rh, int micro) {
   if (cnt <= 0) return hipSuccess;
   if (micro)   // every front of the list has M <= 8
-    SMLU_T(k_ut_micro, nblk_t(cnt, 32), 256, list, cnt, sn, chlist, relmap, store, x, vbuf);
-  SMLU_T(k_ut_tiny, nblk_t(cnt, kTinyWaves), 64 * kTinyWaves, list, cnt, sn, chlist, relmap, store, x, vbuf);
+    SMLU_BY_WIDTH(k_ut_micro, nblk(cnt, 32), 256, list, cnt, sn, chlist, relmap, store, x, vbuf);
+  SMLU_BY_WIDTH(k_ut_tiny, nblk(cnt, kTinyWaves), 64 * kTinyWaves, list, cnt, sn, chlist, relmap, store, x, vbuf);
 }
 hipError_t launch_lt_tiny(hipStream_t st, int cnt, const int32_t* list, const SNode* sn, const int32_t* rows,
                           const int32_t* rowperm, const double* store, double* x, Rhs rh, int micro) {
   if (cnt <= 0) return hipSuccess;
-  if (micro) SMLU_T(k_lt_micro, nblk_t(cnt, 32), 256, list, cnt, sn, rows, rowperm, store, x);
-  SMLU_T(k_lt_tiny, nblk_t(cnt, kTinyWaves), 64 * kTinyWaves, list, cnt, sn, rows, rowperm, store, x);
+  if (micro) SMLU_BY_WIDTH(k_lt_micro, nblk(cnt, 32), 256, list, cnt, sn, rows, rowperm, store, x);
+  SMLU_BY_WIDTH(k_lt_tiny, nblk(cnt, kTinyWaves), 64 * kTinyWaves, list, cnt, sn, rows, rowperm, store, x);
 }
 hipError_t launch_ut_front(hipStream_t st, int cnt, const int32_t* list, const SNode* sn, const int32_t* chlist,
                            const int32_t* relmap, const double* store, double* x, double* vbuf, Rhs rh) {
   if (cnt <= 0) return hipSuccess;
-  SMLU_T(k_ut_front, cnt, 256, list, sn, chlist, relmap, store, x, vbuf);
+  SMLU_BY_WIDTH(k_ut_front, cnt, 256, list, sn, chlist, relmap, store, x, vbuf);
 }
 hipError_t launch_lt_front(hipStream_t st, int cnt, const int32_t* list, const SNode* sn, const int32_t* rows,
                            const int32_t* rowperm, const double* store, double* x, double* vbuf, Rhs rh) {
   if (cnt <= 0) return hipSuccess;
-  SMLU_T(k_lt_front, cnt, 256, list, sn, rows, rowperm, store, x, vbuf);
+  SMLU_BY_WIDTH(k_lt_front, cnt, 256, list, sn, rows, rowperm, store, x, vbuf);
 }
 hipError_t launch_pull_t(hipStream_t st, int64_t nwg, const FrontTile* ft, int nft, const SNode* sn,
                          const int32_t* gptr, const int32_t* gent, const double* x, double* vbuf, Rhs rh) {
   if (nwg <= 0) return hipSuccess;
-  SMLU_T(k_pull_t, (unsigned)nwg, 256, ft, nft, sn, gptr, gent, x, vbuf);
+  SMLU_BY_WIDTH(k_pull_t, (unsigned)nwg, 256, ft, nft, sn, gptr, gent, x, vbuf);
 }
 hipError_t launch_tri_t(hipStream_t st, bool upper, int64_t nwg, const FrontTile* ft, int nft, int step,
                         const SNode* sn, const int32_t* rowperm, const double* store, double* x, double* vbuf,
                         Rhs rh) {
   if (nwg <= 0) return hipSuccess;
-  if (upper) SMLU_T2(k_tri_t, true, (unsigned)nwg, 320, ft, nft, step, sn, rowperm, store, x, vbuf);
-  SMLU_T2(k_tri_t, false, (unsigned)nwg, 320, ft, nft, step, sn, rowperm, store, x, vbuf);
+  if (upper) SMLU_BY_WIDTH2(k_tri_t, true, (unsigned)nwg, 320, ft, nft, step, sn, rowperm, store, x, vbuf);
+  SMLU_BY_WIDTH2(k_tri_t, false, (unsigned)nwg, 320, ft, nft, step, sn, rowperm, store, x, vbuf);
 }
 hipError_t launch_bwdu_t(hipStream_t st, int64_t nwg, const FrontTile* ft, int nft, const SNode* sn,
                          const int32_t* rows, const double* store, const double* x, double* vbuf, Rhs rh) {
   if (nwg <= 0) return hipSuccess;
-  SMLU_T(k_bwdu_t, (unsigned)nwg, 256, ft, nft, sn, rows, store, x, vbuf);
+  SMLU_BY_WIDTH(k_bwdu_t, (unsigned)nwg, 256, ft, nft, sn, rows, store, x, vbuf);
 }
 // column j of b at b + j*ldb, of x at x + j*ldxo; of the work vectors at wrk + j*rh.ldx
 hipError_t launch_perm_in_t(hipStream_t st, int64_t n, const int64_t* q, const double* b, int64_t ldb, double* wrk,
                             int conj, Rhs rh) {
   if (n <= 0) return hipSuccess;
-  SMLU_T(k_perm_in_t, nblk_t(n, 256), 256, n, q, b, ldb, wrk, conj);
+  SMLU_BY_WIDTH(k_perm_in_t, nblk(n, 256), 256, n, q, b, ldb, wrk, conj);
 }
 hipError_t launch_perm_out_t(hipStream_t st, int64_t n, const int64_t* p0, const double* Rs, const double* wrk,
                              double* x, int64_t ldxo, int conj, Rhs rh) {
   if (n <= 0) return hipSuccess;
-  SMLU_T(k_perm_out_t, nblk_t(n, 256), 256, n, p0, Rs, wrk, x, ldxo, conj);
+  SMLU_BY_WIDTH(k_perm_out_t, nblk(n, 256), 256, n, p0, Rs, wrk, x, ldxo, conj);
 }
-#undef SMLU_T
-#undef SMLU_T2
 hipError_t launch_residual_t(hipStream_t st, int64_t n, const int64_t* colptr, const int32_t* arow, const double* a,
                              const double* x, const double* b, double* r, double* nrm, int conj) {
   if (n <= 0) return hipSuccess;
-  k_residual_t<<<nblk_t(n, 256), 256, 0, st>>>(n, colptr, arow, a, x, b, r, nrm, conj);
+  k_residual_t<<<nblk(n, 256), 256, 0, st>>>(n, colptr, arow, a, x, b, r, nrm, conj);
   return hipGetLastError();
 }
 

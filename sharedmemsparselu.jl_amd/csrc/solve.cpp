@@ -109,6 +109,42 @@ static int run_graphed(smlu_handle* h, bool use_graph, int key, F&& body) {
   return SMLU_OK;
 }
 
+// What the two plain passes open and close alike: the host clock behind solve_ms, the profile
+// timer, and the work buffers of the width -- wrk / vbuf for one column, wrkm / vbufm (allocated on
+// first use) for a batch.
+struct Pass {
+  smlu_handle* h;
+  Timer tm;
+  hipEvent_t stop = nullptr;
+  std::chrono::steady_clock::time_point t0;
+  double* w = nullptr;
+  double* v = nullptr;
+  Rhs rh{};
+  explicit Pass(smlu_handle* hh) : h(hh), tm(hh) {}
+  int open(int nrhs) {
+    t0 = std::chrono::steady_clock::now();
+    HIPCHK(tm.begin(K_FWD, &stop, h->stream));
+    w = h->wrk.p;
+    v = h->vbuf.p;
+    rh = Rhs{1, (int64_t)h->plan.n, (int64_t)h->vbuf.n};
+    if (nrhs > 1) {
+      if (!h->vbufm.p) HIPCHK(h->vbufm.alloc(h->vbuf.n * kMultiRhs));
+      if (!h->wrkm.p) HIPCHK(h->wrkm.alloc((size_t)h->plan.n * kMultiRhs));
+      w = h->wrkm.p;
+      v = h->vbufm.p;
+      rh.n = nrhs;
+    }
+    return SMLU_OK;
+  }
+  int close() {   // the pass is complete on return
+    HIPCHK(tm.end(stop));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    tm.collect();
+    return SMLU_OK;
+  }
+  void stamp() { h->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
 int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode, int nrhs, int64_t ldb, int64_t ldx) {
   // mode 0: ldiv (b -> x); 1: lsolve in place on dx (final order); 2: rsolve in place.
   // nrhs > 1 (mode 0, one GPU): columns of db / dx with leading dimensions ldb / ldx.
@@ -117,31 +153,19 @@ int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode, int nr
   if (nrhs > 1 && (mode != 0 || h->nranks > 1 || nrhs > kMultiRhs))
     return fail(h, SMLU_ERR_STATE, "batched right-hand sides: ldiv on one GPU only");
   hipStream_t st = h->stream;
-  auto t0 = std::chrono::steady_clock::now();
-  Timer tm(h);
-  hipEvent_t stop;
-  HIPCHK(tm.begin(K_FWD, &stop, h->stream));
-  double* w = h->wrk.p;
-  double* v = h->vbuf.p;
-  Rhs rh{1, (int64_t)P.n, (int64_t)h->vbuf.n};
-  if (nrhs > 1) {
-    if (!h->vbufm.p) HIPCHK(h->vbufm.alloc(h->vbuf.n * kMultiRhs));
-    if (!h->wrkm.p) HIPCHK(h->wrkm.alloc((size_t)P.n * kMultiRhs));
-    w = h->wrkm.p;
-    v = h->vbufm.p;
-    rh.n = nrhs;
-  }
-  // batches of up to SMLU_SWEEP_MAX_RHS (<= 8) right-hand sides run the sweeps (NR-wide hand-off
-  // slots), wider ones the per-block launches (fwdm / bwdm)
+  Pass ps(h);
+  if (int rc = ps.open(nrhs); rc != SMLU_OK) return rc;
+  double* const w = ps.w;
+  double* const v = ps.v;
+  const Rhs rh = ps.rh;
   // batches of up to 8 run the sweeps too (round 6: the NR substitution chains interleaved,
-  // tri64_rows); wider ones the per-block schedule
-  constexpr int sweep_max_rhs = 8;
-  const bool steps = rh.n > std::min(8, std::max(1, sweep_max_rhs)) && h->nranks == 1;
+  // tri64_rows, NR-wide hand-off slots); wider ones the per-block schedule (fwdm / bwdm)
+  const bool wide = rh.n > 8 && h->nranks == 1;
   // The sync-free sweeps' waits are bounded: a wait that gives up raises sstatus, which is read back
   // after every solve that ran them; the solve is then re-run on the per-block schedule (fwdm / bwdm,
   // bitwise the same arithmetic), so a timed-out sweep never returns a wrong x.  Partitioned handles
   // agree on the re-run (allreduce of the flag: the per-block sequences hold the same comm steps).
-  const bool check = !steps && (h->sch.ssync_n > 0 || h->nranks > 1);
+  const bool check = !wide && (h->sch.ssync_n > 0 || h->nranks > 1);
   const double* src = mode == 0 ? db : dx;
   const int64_t lds = mode == 0 && ldb > 0 ? ldb : P.n;
   auto load_input = [&](const double* in, int64_t ld) -> hipError_t {
@@ -176,13 +200,13 @@ int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode, int nr
     }
     return (int)SMLU_OK;
   };
-  auto sweeps = [&](bool steps) {   // steps: the per-block sequences instead of the sweeps
+  auto sweeps = [&](bool per_block) {   // per_block: the per-block sequences instead of the sweeps
     if (mode != 2) {
-      int rc = steps ? run_seq(h->sch.fwdm, h->sch.fwdm_seg, h->sch.fwd_comm, true) : run_seq(h->sch.fwd, h->sch.fwd_seg, h->sch.fwd_comm, false);
+      int rc = per_block ? run_seq(h->sch.fwdm, h->sch.fwdm_seg, h->sch.fwd_comm, true) : run_seq(h->sch.fwd, h->sch.fwd_seg, h->sch.fwd_comm, false);
       if (rc != SMLU_OK) return rc;
     }
     if (mode != 1) {
-      int rc = steps ? run_seq(h->sch.bwdm, h->sch.bwdm_seg, h->sch.bwd_comm, true) : run_seq(h->sch.bwd, h->sch.bwd_seg, h->sch.bwd_comm, false);
+      int rc = per_block ? run_seq(h->sch.bwdm, h->sch.bwdm_seg, h->sch.bwd_comm, true) : run_seq(h->sch.bwd, h->sch.bwd_seg, h->sch.bwd_comm, false);
       if (rc != SMLU_OK) return rc;
     }
     return (int)SMLU_OK;
@@ -194,13 +218,12 @@ int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode, int nr
   // One GPU: the forward and backward sweeps (~1,400 launches at 128^3, fixed pointers: the
   // handle's wrk / vbuf) are captured once per (mode, rhs count) into a hipGraph and replayed;
   // only the permutation kernels see the caller's b and x.
-  int rc = run_graphed(h, h->nranks == 1 && !tune().no_graph, mode * 256 + rh.n, [&] { return sweeps(steps); });
+  int rc = run_graphed(h, h->nranks == 1 && !tune().no_graph, mode * 256 + rh.n, [&] { return sweeps(wide); });
   if (rc != SMLU_OK) return rc;
   if (mode == 0) ++h->solve_passes;   // a sweep-timeout re-run below is the same pass
   HIPCHK(finish());
-  HIPCHK(tm.end(stop));
-  HIPCHK(hipStreamSynchronize(st));
-  tm.collect();
+  rc = ps.close();
+  if (rc != SMLU_OK) return rc;
   if (check) {
     long long rec[16];
     int rs = read_status(h, nullptr, 0, h->sstatus.p, 1, rec);
@@ -218,10 +241,9 @@ int run_solve_dev(smlu_handle* h, const double* db, double* dx, int mode, int nr
       HIPCHK(hipStreamSynchronize(st));
     }
   }
-  h->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  ps.stamp();
   return SMLU_OK;
 }
-
 
 // ldiv! plus iterative refinement on the original (unscaled) A: x <- x + A \ (b - A x).  The
 // diagonal-tile pivoting of large fronts cannot always keep growth below 1/pivot_tol; when a
@@ -307,14 +329,6 @@ static int solve_refined_by(smlu_handle* h, const double* db, double* dx, SOLVE&
   return SMLU_OK;
 }
 
-static int solve_refined(smlu_handle* h, const double* db, double* dx) {
-  return solve_refined_by(
-      h, db, dx, [&](const double* b, double* x) { return run_solve_dev(h, b, x, 0); },
-      [&](const double* x, const double* b, double* r, double* nrm) {
-        return launch_residual(h->stream, h->plan.n, h->Arowptr.p, h->Arow_ent.p, h->Acol.p, h->A.p, x, b, r, nrm);
-      });
-}
-
 int smlu_residual_device(smlu_handle* h, const double* d_x, const double* d_b, double* d_r, double* nrm) {
   if (!h || !d_x || !d_b || !d_r) return fail(h, SMLU_ERR_ARG, "NULL argument");
   HIPCHK(hipSetDevice(h->device));
@@ -331,98 +345,6 @@ int smlu_residual_device(smlu_handle* h, const double* d_x, const double* d_b, d
   double v;
   std::memcpy(&v, &rec[6], sizeof v);
   if (nrm) *nrm = v;
-  return SMLU_OK;
-}
-
-int smlu_solve_device(smlu_handle* h, const double* d_b, double* d_x) {
-  if (!h || !d_b || !d_x) return fail(h, SMLU_ERR_ARG, "NULL argument");
-  if (!h->have_numeric) return fail(h, SMLU_ERR_STATE, "no numeric factorization");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(after_caller(h));
-  return solve_refined(h, d_b, d_x);
-}
-
-int smlu_solve(smlu_handle* h, const double* b, double* x) {
-  if (!h || !b || !x) return fail(h, SMLU_ERR_ARG, "NULL argument");
-  if (!h->have_numeric) return fail(h, SMLU_ERR_STATE, "no numeric factorization");
-  HIPCHK(hipSetDevice(h->device));
-  int64_t n = h->plan.n;
-  HIPCHK(hipMemcpyAsync(h->wrk2.p, b, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-  int rc = solve_refined(h, h->wrk2.p, h->wrk2.p);
-  if (rc != SMLU_OK) return rc;
-  HIPCHK(hipMemcpyAsync(x, h->wrk2.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return SMLU_OK;
-}
-
-// Multiple right-hand sides.  One GPU without refinement: batches of up to kMultiRhs columns go
-// through the solve kernels together (each factor value read once per batch, not per column);
-// otherwise (refinement, several GPUs) one refined solve per column.  d_B may alias d_X when
-// ldb == ldx (the batch is permuted into the work buffer before x is written).
-static int solve_multi_dev(smlu_handle* h, int64_t nrhs, const double* d_B, int64_t ldb, double* d_X,
-                           int64_t ldx) {
-  const int steps = auto_refine_steps(h);
-  const bool batched = steps == 0 && h->nranks == 1 && nrhs > 1;
-  if (!batched) {
-    for (int64_t j = 0; j < nrhs; ++j) {
-      int rc = solve_refined(h, d_B + j * ldb, d_X + j * ldx);
-      if (rc != SMLU_OK) return rc;
-    }
-    return SMLU_OK;
-  }
-  h->refine_steps = 0;
-  h->refine_resid = -1;
-  h->refine_berr = -1;
-  double ms = 0;
-  for (int64_t j = 0; j < nrhs; j += kMultiRhs) {
-    const int nb = (int)std::min<int64_t>(kMultiRhs, nrhs - j);
-    int rc = run_solve_dev(h, d_B + j * ldb, d_X + j * ldx, 0, nb, ldb, ldx);
-    if (rc != SMLU_OK) return rc;
-    ms += h->solve_ms;
-  }
-  h->solve_ms = ms;
-  return SMLU_OK;
-}
-
-int smlu_solve_multi_device(smlu_handle* h, int64_t nrhs, const double* d_B, int64_t ldb, double* d_X,
-                            int64_t ldx) {
-  if (!h || nrhs < 0 || (nrhs > 0 && (!d_B || !d_X))) return fail(h, SMLU_ERR_ARG, "invalid arguments");
-  if (!h->have_numeric) return fail(h, SMLU_ERR_STATE, "no numeric factorization");
-  const int64_t n = h->plan.n;
-  if (ldb < n || ldx < n) return fail(h, SMLU_ERR_ARG, "leading dimension smaller than n");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(after_caller(h));
-  return solve_multi_dev(h, nrhs, d_B, ldb, d_X, ldx);
-}
-
-int smlu_solve_multi(smlu_handle* h, int64_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx) {
-  if (!h || nrhs < 0 || (nrhs > 0 && (!B || !X))) return fail(h, SMLU_ERR_ARG, "invalid arguments");
-  if (!h->have_numeric) return fail(h, SMLU_ERR_STATE, "no numeric factorization");
-  const int64_t n = h->plan.n;
-  if (ldb < n || ldx < n) return fail(h, SMLU_ERR_ARG, "leading dimension smaller than n");
-  HIPCHK(hipSetDevice(h->device));
-  if (nrhs > 1 && h->nranks == 1 && auto_refine_steps(h) == 0) {
-    if (!h->wrk2m.p) HIPCHK(h->wrk2m.alloc((size_t)n * kMultiRhs));
-    double* d = h->wrk2m.p;
-    for (int64_t j = 0; j < nrhs; j += kMultiRhs) {
-      const int64_t nb = std::min<int64_t>(kMultiRhs, nrhs - j);
-      HIPCHK(hipMemcpy2DAsync(d, sizeof(double) * n, B + j * ldb, sizeof(double) * ldb, sizeof(double) * n, nb,
-                              hipMemcpyHostToDevice, h->stream));
-      int rc = solve_multi_dev(h, nb, d, n, d, n);
-      if (rc != SMLU_OK) return rc;
-      HIPCHK(hipMemcpy2DAsync(X + j * ldx, sizeof(double) * ldx, d, sizeof(double) * n, sizeof(double) * n, nb,
-                              hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return SMLU_OK;
-  }
-  for (int64_t j = 0; j < nrhs; ++j) {
-    HIPCHK(hipMemcpyAsync(h->wrk2.p, B + j * ldb, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-    int rc = solve_refined(h, h->wrk2.p, h->wrk2.p);
-    if (rc != SMLU_OK) return rc;
-    HIPCHK(hipMemcpyAsync(X + j * ldx, h->wrk2.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-  }
-  HIPCHK(hipStreamSynchronize(h->stream));
   return SMLU_OK;
 }
 
@@ -472,20 +394,12 @@ int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* dx, int 
   Plan& P = h->plan;
   if (nrhs < 1 || nrhs > kMultiRhs) return fail(h, SMLU_ERR_STATE, "transposed batch: 1 to 16 right-hand sides");
   hipStream_t st = h->stream;
-  auto t0 = std::chrono::steady_clock::now();
-  Timer tm(h);
-  hipEvent_t stop;
-  HIPCHK(tm.begin(K_FWD, &stop, st));
-  double* w = h->wrk.p;
-  double* v = h->vbuf.p;
-  Rhs rh{1, (int64_t)P.n, (int64_t)h->vbuf.n};
-  if (nrhs > 1) {
-    if (!h->vbufm.p) HIPCHK(h->vbufm.alloc(h->vbuf.n * kMultiRhs));
-    if (!h->wrkm.p) HIPCHK(h->wrkm.alloc((size_t)P.n * kMultiRhs));
-    w = h->wrkm.p;
-    v = h->vbufm.p;
-    rh.n = nrhs;
-  }
+  Pass ps(h);
+  int rc = ps.open(nrhs);
+  if (rc != SMLU_OK) return rc;
+  double* const w = ps.w;
+  double* const v = ps.v;
+  const Rhs rh = ps.rh;
   HIPCHK(launch_perm_in_t(st, P.n, h->q.p, db, ldb, w, conj, rh));
   auto launch = [&](const Launch& L, hipStream_t s) { return run_solve_launch_t(h, L, w, v, rh, s); };
   auto passes = [&]() {   // the whole of fwdm, then of bwdm, with the side-stream overlap
@@ -495,145 +409,117 @@ int run_solve_t_dev(smlu_handle* h, int conj, const double* db, double* dx, int 
     return (int)SMLU_OK;
   };
   // the two passes (fixed pointers: the handle's wrk / vbuf, or wrkm / vbufm), one graph per batch width
-  int rc = run_graphed(h, !tune().no_graph, kTransGraphKey + rh.n, passes);
+  rc = run_graphed(h, !tune().no_graph, kTransGraphKey + rh.n, passes);
   if (rc != SMLU_OK) return rc;
   ++h->trans_passes;
   HIPCHK(launch_perm_out_t(st, P.n, h->p0.p, h->Rs.p, w, dx, ldx, conj, rh));
-  HIPCHK(tm.end(stop));
-  HIPCHK(hipStreamSynchronize(st));
-  tm.collect();
-  h->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  rc = ps.close();
+  if (rc != SMLU_OK) return rc;
+  ps.stamp();
   return SMLU_OK;
 }
 
-// The transposed solve with solve_refined's refinement rule: r = b - A^T x by columns of A's CSC,
+// ---- the front end of the smlu_solve* entry points ---------------------------------------------
+// The operation of a call, filled by check_solve.
+struct SolveOp {
+  bool trans = false;   // A^T x = b or A^H x = b: the transposed passes and residual
+  int conj = 0;         // ... conjugated in and out (the plain transpose of a ComplexF64 handle)
+};
+
+// Argument and state checks of the ten smlu_solve* entry points.  refined: the batched-refinement
+// pair, which takes max_steps and, as smlu_logabsdet, refuses the handle of a singular factorization.
+static int check_solve(smlu_handle* h, int op, bool refined, int max_steps, int64_t nrhs, const double* B, int64_t ldb,
+                       const double* X, int64_t ldx, SolveOp* o) {
+  if (!h || nrhs < 0 || (nrhs > 0 && (!B || !X))) return fail(h, SMLU_ERR_ARG, "NULL argument or nrhs < 0");
+  if (op != SMLU_OP_N && op != SMLU_OP_T && op != SMLU_OP_H)
+    return fail(h, SMLU_ERR_ARG, "op must be SMLU_OP_N, SMLU_OP_T or SMLU_OP_H");
+  if (max_steps < -1) return fail(h, SMLU_ERR_ARG, "max_steps must be -1 (the handle's rule), 0 or a step limit");
+  if (!h->have_numeric || (refined && h->errcol >= 0))
+    return fail(h, SMLU_ERR_STATE, "no numeric factorization (none yet, or a singular one)");
+  if (h->nranks > 1 && (op != SMLU_OP_N || refined))
+    return fail(h, SMLU_ERR_STATE, "transposed solves and batched refinement are single-GPU only");
+  if (ldb < h->plan.n || ldx < h->plan.n) return fail(h, SMLU_ERR_ARG, "leading dimension smaller than n");
+  o->trans = op != SMLU_OP_N;
+  o->conj = h->zc && op == SMLU_OP_T;
+  return SMLU_OK;
+}
+
+// One plain pass over w <= kMultiRhs columns (one column: the leading dimensions are unused).
+static int plain_pass(smlu_handle* h, const SolveOp& o, const double* b, double* x, int w, int64_t ldb, int64_t ldx) {
+  return o.trans ? run_solve_t_dev(h, o.conj, b, x, w, ldb, ldx) : run_solve_dev(h, b, x, 0, w, ldb, ldx);
+}
+
+// One refined column.  Transposed: solve_refined_by's rule with r = b - A^T x by columns of A's CSC,
 // componentwise denominator |A^T||x| + |b|, same stop test and the same refine_* stats.
-static int solve_refined_t(smlu_handle* h, int conj, const double* db, double* dx) {
+static int refined_column(smlu_handle* h, const SolveOp& o, const double* db, double* dx) {
   Plan& P = h->plan;
-  if (auto_refine_steps(h) != 0 && !h->Acolp.p)
+  if (o.trans && auto_refine_steps(h) != 0 && !h->Acolp.p)
     HIPCHK(h->Acolp.upload(P.Acolptr.data(), P.Acolptr.size(), h->stream));
   return solve_refined_by(
-      h, db, dx, [&](const double* b, double* x) { return run_solve_t_dev(h, conj, b, x); },
+      h, db, dx, [&](const double* b, double* x) { return plain_pass(h, o, b, x, 1, 0, 0); },
       [&](const double* x, const double* b, double* r, double* nrm) {
-        return launch_residual_t(h->stream, P.n, h->Acolp.p, h->Arow.p, h->A.p, x, b, r, nrm, conj);
+        return o.trans ? launch_residual_t(h->stream, P.n, h->Acolp.p, h->Arow.p, h->A.p, x, b, r, nrm, o.conj)
+                       : launch_residual(h->stream, P.n, h->Arowptr.p, h->Arow_ent.p, h->Acol.p, h->A.p, x, b, r, nrm);
       });
 }
 
-// op and handle checks shared by the four entry points; *conj: conjugate in and out
-static int trans_check(smlu_handle* h, int op, int* conj) {
-  if (op != SMLU_OP_T && op != SMLU_OP_H) return fail(h, SMLU_ERR_ARG, "op must be SMLU_OP_N, SMLU_OP_T or SMLU_OP_H");
-  if (!h->have_numeric) return fail(h, SMLU_ERR_STATE, "no numeric factorization");
-  if (h->nranks > 1) return fail(h, SMLU_ERR_STATE, "transposed solves are single-GPU only");
-  *conj = h->zc && op == SMLU_OP_T;
-  return SMLU_OK;
-}
+// The columns of a call: device pointers, or host memory staged through the handle.
+struct Cols {
+  const double* B;
+  int64_t ldb;
+  double* X;
+  int64_t ldx;
+  bool host;
+};
 
-int smlu_solve_trans_device(smlu_handle* h, int op, const double* d_b, double* d_x) {
-  if (!h || !d_b || !d_x) return fail(h, SMLU_ERR_ARG, "NULL argument");
-  if (op == SMLU_OP_N) return smlu_solve_device(h, d_b, d_x);
-  int conj = 0;
-  int rc = trans_check(h, op, &conj);
-  if (rc != SMLU_OK) return rc;
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(after_caller(h));
-  return solve_refined_t(h, conj, d_b, d_x);
-}
-
-int smlu_solve_trans(smlu_handle* h, int op, const double* b, double* x) {
-  if (!h || !b || !x) return fail(h, SMLU_ERR_ARG, "NULL argument");
-  if (op == SMLU_OP_N) return smlu_solve(h, b, x);
-  int conj = 0;
-  int rc = trans_check(h, op, &conj);
-  if (rc != SMLU_OK) return rc;
-  HIPCHK(hipSetDevice(h->device));
+// body(b, ldb, x, ldx, j, nb) on device pointers for every chunk [j, j + nb) of up to width columns.
+// Host columns are copied into the handle's staging buffer (wrk2 at width 1, else wrk2m, allocated on
+// first use), solved there in place and copied back, with one synchronisation after the last chunk;
+// a single column moves by a plain copy.
+template <class F>
+static int over_chunks(smlu_handle* h, const Cols& c, int64_t nrhs, int width, F&& body) {
   const int64_t n = h->plan.n;
-  HIPCHK(hipMemcpyAsync(h->wrk2.p, b, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-  rc = solve_refined_t(h, conj, h->wrk2.p, h->wrk2.p);
-  if (rc != SMLU_OK) return rc;
-  HIPCHK(hipMemcpyAsync(x, h->wrk2.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  hipStream_t st = h->stream;
+  if (c.host && width > 1 && !h->wrk2m.p) HIPCHK(h->wrk2m.alloc((size_t)n * kMultiRhs));
+  double* d = width > 1 ? h->wrk2m.p : h->wrk2.p;
+  auto copy = [&](double* dst, int64_t ldd, const double* src, int64_t lds, int nb, hipMemcpyKind kind) {
+    if (nb == 1) return hipMemcpyAsync(dst, src, sizeof(double) * n, kind, st);
+    return hipMemcpy2DAsync(dst, sizeof(double) * ldd, src, sizeof(double) * lds, sizeof(double) * n, (size_t)nb, kind, st);
+  };
+  for (int64_t j = 0; j < nrhs; j += width) {
+    const int nb = (int)std::min<int64_t>(width, nrhs - j);
+    const double* Bj = c.B + j * c.ldb;
+    double* Xj = c.X + j * c.ldx;
+    if (c.host) HIPCHK(copy(d, n, Bj, c.ldb, nb, hipMemcpyHostToDevice));
+    int rc = c.host ? body(d, n, d, n, j, nb) : body(Bj, c.ldb, Xj, c.ldx, j, nb);
+    if (rc != SMLU_OK) return rc;
+    if (c.host) HIPCHK(copy(Xj, c.ldx, d, n, nb, hipMemcpyDeviceToHost));
+  }
+  if (c.host) HIPCHK(hipStreamSynchronize(st));
   return SMLU_OK;
 }
 
-// Several right-hand sides.  Without refinement, batches of up to kMultiRhs columns go through the
-// transposed kernels together (each factor value read once per batch; every column bitwise its
-// single-vector solve); otherwise one refined transposed solve per column.  d_B may alias d_X when
-// ldb == ldx.
-static int solve_trans_multi_dev(smlu_handle* h, int conj, int64_t nrhs, const double* d_B, int64_t ldb, double* d_X,
-                                 int64_t ldx) {
-  double ms = 0;
-  if (auto_refine_steps(h) != 0 || nrhs <= 1) {
-    for (int64_t j = 0; j < nrhs; ++j) {
-      int rc = solve_refined_t(h, conj, d_B + j * ldb, d_X + j * ldx);
-      if (rc != SMLU_OK) return rc;
-      ms += h->solve_ms;
-    }
-  } else {
+// The driver of the plain entry points.  One GPU without refinement: batches of up to kMultiRhs
+// columns go through the solve kernels together (each factor value read once per batch, not per
+// column; every column bitwise its single-vector solve); otherwise (refinement, several GPUs, one
+// column) one refined solve per column.  B may alias X when ldb == ldx (a batch is permuted into the
+// work buffer before any x is written).  solve_ms: the sum over what the call ran.
+static int solve_cols(smlu_handle* h, const SolveOp& o, const Cols& c, int64_t nrhs) {
+  const bool batched = auto_refine_steps(h) == 0 && h->nranks == 1 && nrhs > 1;
+  if (batched) {
     h->refine_steps = 0;
     h->refine_resid = -1;
     h->refine_berr = -1;
-    for (int64_t j = 0; j < nrhs; j += kMultiRhs) {
-      const int nb = (int)std::min<int64_t>(kMultiRhs, nrhs - j);
-      int rc = run_solve_t_dev(h, conj, d_B + j * ldb, d_X + j * ldx, nb, ldb, ldx);
-      if (rc != SMLU_OK) return rc;
-      ms += h->solve_ms;
-    }
   }
-  if (nrhs > 0) h->solve_ms = ms;
-  return SMLU_OK;
-}
-
-int smlu_solve_trans_multi_device(smlu_handle* h, int op, int64_t nrhs, const double* d_B, int64_t ldb, double* d_X,
-                                  int64_t ldx) {
-  if (!h || nrhs < 0 || (nrhs > 0 && (!d_B || !d_X))) return fail(h, SMLU_ERR_ARG, "invalid arguments");
-  if (op == SMLU_OP_N) return smlu_solve_multi_device(h, nrhs, d_B, ldb, d_X, ldx);
-  int conj = 0;
-  int rc = trans_check(h, op, &conj);
-  if (rc != SMLU_OK) return rc;
-  const int64_t n = h->plan.n;
-  if (ldb < n || ldx < n) return fail(h, SMLU_ERR_ARG, "leading dimension smaller than n");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(after_caller(h));
-  return solve_trans_multi_dev(h, conj, nrhs, d_B, ldb, d_X, ldx);
-}
-
-int smlu_solve_trans_multi(smlu_handle* h, int op, int64_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx) {
-  if (!h || nrhs < 0 || (nrhs > 0 && (!B || !X))) return fail(h, SMLU_ERR_ARG, "invalid arguments");
-  if (op == SMLU_OP_N) return smlu_solve_multi(h, nrhs, B, ldb, X, ldx);
-  int conj = 0;
-  int rc = trans_check(h, op, &conj);
-  if (rc != SMLU_OK) return rc;
-  const int64_t n = h->plan.n;
-  if (ldb < n || ldx < n) return fail(h, SMLU_ERR_ARG, "leading dimension smaller than n");
-  HIPCHK(hipSetDevice(h->device));
   double ms = 0;
-  if (nrhs > 1 && auto_refine_steps(h) == 0) {   // batches staged through wrk2m, as smlu_solve_multi
-    if (!h->wrk2m.p) HIPCHK(h->wrk2m.alloc((size_t)n * kMultiRhs));
-    double* d = h->wrk2m.p;
-    for (int64_t j = 0; j < nrhs; j += kMultiRhs) {
-      const int64_t nb = std::min<int64_t>(kMultiRhs, nrhs - j);
-      HIPCHK(hipMemcpy2DAsync(d, sizeof(double) * n, B + j * ldb, sizeof(double) * ldb, sizeof(double) * n, nb,
-                              hipMemcpyHostToDevice, h->stream));
-      rc = solve_trans_multi_dev(h, conj, nb, d, n, d, n);
-      if (rc != SMLU_OK) return rc;
-      ms += h->solve_ms;
-      HIPCHK(hipMemcpy2DAsync(X + j * ldx, sizeof(double) * ldx, d, sizeof(double) * n, sizeof(double) * n, nb,
-                              hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->solve_ms = ms;
-    return SMLU_OK;
-  }
-  for (int64_t j = 0; j < nrhs; ++j) {
-    HIPCHK(hipMemcpyAsync(h->wrk2.p, B + j * ldb, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-    rc = solve_refined_t(h, conj, h->wrk2.p, h->wrk2.p);
-    if (rc != SMLU_OK) return rc;
-    ms += h->solve_ms;
-    HIPCHK(hipMemcpyAsync(X + j * ldx, h->wrk2.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-  }
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (nrhs > 0) h->solve_ms = ms;
-  return SMLU_OK;
+  int rc = over_chunks(h, c, nrhs, batched ? kMultiRhs : 1,
+                       [&](const double* b, int64_t ldb, double* x, int64_t ldx, int64_t, int nb) {
+                         int r = batched ? plain_pass(h, o, b, x, nb, ldb, ldx) : refined_column(h, o, b, x);
+                         ms += h->solve_ms;
+                         return r;
+                       });
+  if (rc == SMLU_OK) h->solve_ms = ms;
+  return rc;
 }
 
 // ---- batched iterative refinement: smlu_solve_refined_multi*  ----------------------
@@ -749,33 +635,30 @@ static int refine_batch(smlu_handle* h, int steps, int nb, const double* dB, int
   return SMLU_OK;
 }
 
-// All batches of a call on device pointers (op checked, conj set); info may be NULL.
-static int solve_refined_multi_dev(smlu_handle* h, int op, int conj, int steps, int64_t nrhs, const double* d_B,
-                                   int64_t ldb, double* d_X, int64_t ldx, smlu_refine_info* info) {
+// The driver of the refined pair: every batch of a call refined as a batch; info may be NULL.  The
+// refine_* stats hold the largest over the call's columns, solve_ms the sum of the batches' first solves.
+static int refined_cols(smlu_handle* h, const SolveOp& o, int steps, const Cols& c, int64_t nrhs,
+                        smlu_refine_info* info) {
   Plan& P = h->plan;
-  const bool trans = op != SMLU_OP_N;
   if (steps > 0) {
-    int rc = ensure_refine_batch(h, trans);
+    int rc = ensure_refine_batch(h, o.trans);
     if (rc != SMLU_OK) return rc;
   }
-  auto solve = [&](const double* b, int64_t lb, double* x, int64_t lx, int w) {
-    return trans ? run_solve_t_dev(h, conj, b, x, w, lb, lx) : run_solve_dev(h, b, x, 0, w, lb, lx);
-  };
+  auto solve = [&](const double* b, int64_t lb, double* x, int64_t lx, int w) { return plain_pass(h, o, b, x, w, lb, lx); };
   auto residual = [&](const double* x, int64_t lx, const double* b, double* r, double* nrm, int nact,
                       const int32_t* list) {
-    return trans ? launch_residual_t_batch(h->stream, P.n, h->Acolp.p, h->Arow.p, h->A.p, x, lx, b, r, nrm, conj, nact,
-                                           list)
-                 : launch_residual_batch(h->stream, P.n, h->Arowptr.p, h->Arow_ent.p, h->Acol.p, h->A.p, x, lx, b, r,
-                                         nrm, nact, list);
+    return o.trans ? launch_residual_t_batch(h->stream, P.n, h->Acolp.p, h->Arow.p, h->A.p, x, lx, b, r, nrm, o.conj,
+                                             nact, list)
+                   : launch_residual_batch(h->stream, P.n, h->Arowptr.p, h->Arow_ent.p, h->Acol.p, h->A.p, x, lx, b, r,
+                                           nrm, nact, list);
   };
   int max_steps = 0;
   double max_berr = -1, max_resid = -1, ms = 0;
-  for (int64_t j = 0; j < nrhs; j += kMultiRhs) {
-    const int nb = (int)std::min<int64_t>(kMultiRhs, nrhs - j);
+  int rc = over_chunks(h, c, nrhs, kMultiRhs, [&](const double* b, int64_t ldb, double* x, int64_t ldx, int64_t j, int nb) {
     smlu_refine_info bi[kMultiRhs];
     double bms = 0;
-    int rc = refine_batch(h, steps, nb, d_B + j * ldb, ldb, d_X + j * ldx, ldx, bi, &bms, solve, residual);
-    if (rc != SMLU_OK) return rc;
+    int r = refine_batch(h, steps, nb, b, ldb, x, ldx, bi, &bms, solve, residual);
+    if (r != SMLU_OK) return r;
     ms += bms;
     for (int k = 0; k < nb; ++k) {
       max_steps = std::max(max_steps, (int)bi[k].steps);
@@ -783,7 +666,9 @@ static int solve_refined_multi_dev(smlu_handle* h, int op, int conj, int steps, 
       max_resid = std::max(max_resid, bi[k].resid);
       if (info) info[j + k] = bi[k];
     }
-  }
+    return (int)SMLU_OK;
+  });
+  if (rc != SMLU_OK) return rc;
   h->refine_steps = max_steps;
   h->refine_berr = max_berr;
   h->refine_resid = max_resid;
@@ -791,76 +676,65 @@ static int solve_refined_multi_dev(smlu_handle* h, int op, int conj, int steps, 
   return SMLU_OK;
 }
 
-// argument and state checks of the two entry points (smlu_solve_trans_multi*'s, and max_steps)
-static int refined_multi_check(smlu_handle* h, int op, int max_steps, int64_t nrhs, const double* B, int64_t ldb,
-                               const double* X, int64_t ldx, int* conj, int* steps) {
-  if (!h || nrhs < 0 || (nrhs > 0 && (!B || !X))) return fail(h, SMLU_ERR_ARG, "invalid arguments");
-  if (op != SMLU_OP_N && op != SMLU_OP_T && op != SMLU_OP_H)
-    return fail(h, SMLU_ERR_ARG, "op must be SMLU_OP_N, SMLU_OP_T or SMLU_OP_H");
-  if (max_steps < -1) return fail(h, SMLU_ERR_ARG, "max_steps must be -1 (the handle's rule), 0 or a step limit");
-  if (!h->have_numeric || h->errcol >= 0)
-    return fail(h, SMLU_ERR_STATE, "no numeric factorization (none yet, or a singular one)");
-  if (h->nranks > 1) return fail(h, SMLU_ERR_STATE, "batched refinement is single-GPU only");
-  const int64_t n = h->plan.n;
-  if (ldb < n || ldx < n) return fail(h, SMLU_ERR_ARG, "leading dimension smaller than n");
-  *conj = h->zc && op == SMLU_OP_T;
-  *steps = max_steps < 0 ? auto_refine_steps(h) : max_steps;
-  return SMLU_OK;
-}
-
-int smlu_solve_refined_multi_device(smlu_handle* h, int op, int max_steps, int64_t nrhs, const double* d_B,
-                                    int64_t ldb, double* d_X, int64_t ldx, smlu_refine_info* info) {
-  int conj = 0, steps = 0;
-  int rc = refined_multi_check(h, op, max_steps, nrhs, d_B, ldb, d_X, ldx, &conj, &steps);
+// Behind every smlu_solve* entry point: the checks, then the columns through their driver.  The
+// _device forms (host false) are ordered after the caller's stream.  refined: the batched-refinement
+// pair with its max_steps and info; nrhs = 0 touches nothing.
+static int solve_call(smlu_handle* h, int op, int64_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx,
+                      bool host, bool refined = false, int max_steps = -1, smlu_refine_info* info = nullptr) {
+  SolveOp o;
+  int rc = check_solve(h, op, refined, max_steps, nrhs, B, ldb, X, ldx, &o);
   if (rc != SMLU_OK || nrhs == 0) return rc;
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(after_caller(h));
-  return solve_refined_multi_dev(h, op, conj, steps, nrhs, d_B, ldb, d_X, ldx, info);
+  if (!host) HIPCHK(after_caller(h));
+  const Cols c{B, ldb, X, ldx, host};
+  if (!refined) return solve_cols(h, o, c, nrhs);
+  return refined_cols(h, o, max_steps < 0 ? auto_refine_steps(h) : max_steps, c, nrhs, info);
 }
 
+// a single vector is one column of leading dimension n
+static int64_t dim(const smlu_handle* h) { return h ? h->plan.n : 0; }
+
+int smlu_solve(smlu_handle* h, const double* b, double* x) {
+  return solve_call(h, SMLU_OP_N, 1, b, dim(h), x, dim(h), true);
+}
+int smlu_solve_device(smlu_handle* h, const double* d_b, double* d_x) {
+  return solve_call(h, SMLU_OP_N, 1, d_b, dim(h), d_x, dim(h), false);
+}
+int smlu_solve_multi(smlu_handle* h, int64_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx) {
+  return solve_call(h, SMLU_OP_N, nrhs, B, ldb, X, ldx, true);
+}
+int smlu_solve_multi_device(smlu_handle* h, int64_t nrhs, const double* d_B, int64_t ldb, double* d_X,
+                            int64_t ldx) {
+  return solve_call(h, SMLU_OP_N, nrhs, d_B, ldb, d_X, ldx, false);
+}
+int smlu_solve_trans(smlu_handle* h, int op, const double* b, double* x) {
+  return solve_call(h, op, 1, b, dim(h), x, dim(h), true);
+}
+int smlu_solve_trans_device(smlu_handle* h, int op, const double* d_b, double* d_x) {
+  return solve_call(h, op, 1, d_b, dim(h), d_x, dim(h), false);
+}
+int smlu_solve_trans_multi(smlu_handle* h, int op, int64_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx) {
+  return solve_call(h, op, nrhs, B, ldb, X, ldx, true);
+}
+int smlu_solve_trans_multi_device(smlu_handle* h, int op, int64_t nrhs, const double* d_B, int64_t ldb, double* d_X,
+                                  int64_t ldx) {
+  return solve_call(h, op, nrhs, d_B, ldb, d_X, ldx, false);
+}
 int smlu_solve_refined_multi(smlu_handle* h, int op, int max_steps, int64_t nrhs, const double* B, int64_t ldb,
                              double* X, int64_t ldx, smlu_refine_info* info) {
-  int conj = 0, steps = 0;
-  int rc = refined_multi_check(h, op, max_steps, nrhs, B, ldb, X, ldx, &conj, &steps);
-  if (rc != SMLU_OK || nrhs == 0) return rc;
-  HIPCHK(hipSetDevice(h->device));
-  const int64_t n = h->plan.n;
-  if (!h->wrk2m.p) HIPCHK(h->wrk2m.alloc((size_t)n * kMultiRhs));   // batches staged as in smlu_solve_multi
-  double* d = h->wrk2m.p;
-  int max_steps_seen = 0;
-  double max_berr = -1, max_resid = -1, ms = 0;
-  for (int64_t j = 0; j < nrhs; j += kMultiRhs) {
-    const int64_t nb = std::min<int64_t>(kMultiRhs, nrhs - j);
-    HIPCHK(hipMemcpy2DAsync(d, sizeof(double) * n, B + j * ldb, sizeof(double) * ldb, sizeof(double) * n, nb,
-                            hipMemcpyHostToDevice, h->stream));
-    rc = solve_refined_multi_dev(h, op, conj, steps, nb, d, n, d, n, info ? info + j : nullptr);
-    if (rc != SMLU_OK) return rc;
-    max_steps_seen = std::max(max_steps_seen, h->refine_steps);
-    max_berr = std::max(max_berr, h->refine_berr);
-    max_resid = std::max(max_resid, h->refine_resid);
-    ms += h->solve_ms;
-    HIPCHK(hipMemcpy2DAsync(X + j * ldx, sizeof(double) * ldx, d, sizeof(double) * n, sizeof(double) * n, nb,
-                            hipMemcpyDeviceToHost, h->stream));
-  }
-  HIPCHK(hipStreamSynchronize(h->stream));
-  h->refine_steps = max_steps_seen;
-  h->refine_berr = max_berr;
-  h->refine_resid = max_resid;
-  h->solve_ms = ms;
-  return SMLU_OK;
+  return solve_call(h, op, nrhs, B, ldb, X, ldx, true, true, max_steps, info);
+}
+int smlu_solve_refined_multi_device(smlu_handle* h, int op, int max_steps, int64_t nrhs, const double* d_B,
+                                    int64_t ldb, double* d_X, int64_t ldx, smlu_refine_info* info) {
+  return solve_call(h, op, nrhs, d_B, ldb, d_X, ldx, false, true, max_steps, info);
 }
 
 static int tri_solve_host(smlu_handle* h, double* x, int mode) {
   if (!h || !x) return fail(h, SMLU_ERR_ARG, "NULL argument");
   if (!h->have_numeric) return fail(h, SMLU_ERR_STATE, "no numeric factorization");
   HIPCHK(hipSetDevice(h->device));
-  int64_t n = h->plan.n;
-  HIPCHK(hipMemcpyAsync(h->wrk2.p, x, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-  int rc = run_solve_dev(h, nullptr, h->wrk2.p, mode);
-  if (rc != SMLU_OK) return rc;
-  HIPCHK(hipMemcpyAsync(x, h->wrk2.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return SMLU_OK;
+  return over_chunks(h, Cols{x, h->plan.n, x, h->plan.n, true}, 1, 1,
+                     [&](const double*, int64_t, double* d, int64_t, int64_t, int) { return run_solve_dev(h, nullptr, d, mode); });
 }
 
 int smlu_lsolve(smlu_handle* h, double* x) { return tri_solve_host(h, x, 1); }
@@ -979,12 +853,9 @@ int smlu_chunked_ldiv(smlu_handle* h, const double* b, double* x) {
   if (!h || !b || !x) return fail(h, SMLU_ERR_ARG, "NULL argument");
   if (!h->have_numeric) return fail(h, SMLU_ERR_STATE, "no numeric factorization");
   HIPCHK(hipSetDevice(h->device));
-  const int64_t n = h->plan.n;
-  HIPCHK(hipMemcpyAsync(h->wrk2.p, b, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-  int rc = smlu_chunked_ldiv_device(h, h->wrk2.p, h->wrk2.p);
-  if (rc != SMLU_OK) return rc;
-  HIPCHK(hipMemcpyAsync(x, h->wrk2.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return SMLU_OK;
+  return over_chunks(h, Cols{b, h->plan.n, x, h->plan.n, true}, 1, 1,
+                     [&](const double* db, int64_t, double* dx, int64_t, int64_t, int) {
+                       return smlu_chunked_ldiv_device(h, db, dx);
+                     });
 }
 

@@ -7,7 +7,7 @@ the same handle; and once per matrix the batch is held against a reference that 
 (tests/_batch_ref.py: the fixed-pivot oracle's unrefined ldiv on the GPU's pivot order, componentwise
 backward error within 4x of the oracle's or under 2^-51, and agreement in norm), so that both being
 wrong is caught.  Every handle is created with refine=0: under the default options a non-dominant
-matrix is refined, and solve_multi_dev then goes column by column, which would compare the
+matrix is refined, and solve_cols then goes column by column, which would compare the
 single-vector solve with itself.  Every batch asserts through the "solve_passes" stat that the batch
 kernels ran: ceil(nrhs / 16) passes per call.  Outputs start as NaN.
 

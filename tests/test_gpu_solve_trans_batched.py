@@ -225,7 +225,7 @@ def test_neighbouring_forward_batches(p12):
 # ---- every kernel --------------------------------------------------------------------------------
 def check_unrefined_batches(A, trans="T", label="", tol=None, **handle_kw):
     """A second handle with refine=0: under the default options a non-dominant matrix is refined and
-    solve_trans_multi_dev goes column by column, so check_batch above compares the single-vector
+    solve_cols goes column by column, so check_batch above compares the single-vector
     solve with itself there.  On this handle a batch of 8 is one pass of the batch kernels, widths 5,
     9 and 16 are bitwise their single solves, and the 5-wide batch is held against unrefined host
     solves from the exported factors (tests/_batch_ref.py)."""
