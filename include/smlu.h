@@ -539,6 +539,16 @@ int smlu_plan_schedule_digest(const smlu_plan* plan, int32_t nparts, int32_t ran
  *                      off the panel chain, and join them before the block's trailing update (one
  *                      GPU, dominant values; bitwise the same factors); 0: off.  smlu_stat:
  *                      side_launches, side_rows
+ *   SMLU_TRAIL_SPAN=s  trailing updates of the large diagonal-tile fronts in tree order: after j
+ *                      finished outer blocks only the blocks of the next lowbit(j) block rows and
+ *                      columns are updated, with k = lowbit(j) outer blocks, and every s-th boundary
+ *                      updates everything right of it with k = s outer blocks (s a power of two,
+ *                      default 2; 1: one k = OB update of everything per outer block, the order
+ *                      before round 11; 0: no full update).  Same launches, same FMA sequence per element, bitwise the same
+ *                      factors (one GPU, dominant values).  smlu_stat: trail_span, trail_fronts,
+ *                      gemmo_kmax
+ *   SMLU_TRAIL_NS=n    ... for fronts with at least n pivot columns (default 1024, and held at or
+ *                      above 1024; 64 is accepted as the lower bound for tests)
  *   SMLU_SWEEP_SPIN=s  polls before a sync-free solve wait gives up and the solve is re-run on the
  *                      per-block schedule (default 2^22; 0 = at once, tests)
  *   SMLU_SOLVE_STEPS=1 per-block solve launches instead of the sync-free sweeps

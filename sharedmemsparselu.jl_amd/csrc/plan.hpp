@@ -27,6 +27,8 @@ struct Tune {
   int64_t f22_gather_nu = 512;  // SMLU_F22_GATHER_NU: fronts with nu >= this have their F22 assembled by the Schur GEMM (<= 0: off)
   int64_t f22_gather_ch = 8;    // SMLU_F22_GATHER_CH: ... if at most this many children contribute
   int64_t lside_min = 2048;   // SMLU_LSIDE_MIN: GEMM-form fronts with at least this many rows below the outer block solve and update those L rows on the side stream (0: off)
+  int trail_span = 2;         // SMLU_TRAIL_SPAN: trailing updates of the qualifying fronts in tree order, full updates every this many outer blocks (a power of two; 1: one full update per outer block; 0: none, unbounded)
+  int64_t trail_ns = 1024;    // SMLU_TRAIL_NS: ... of the diagonal-tile fronts with at least this many pivots (at least 1024; tests: 64)
   int sweep_spin = 1 << 22;  // SMLU_SWEEP_SPIN: polls before a sync-free solve wait gives up (0: at once)
   bool solve_steps = false;   // SMLU_SOLVE_STEPS=1: per-block solve launches instead of the sweeps
   bool no_graph = false;      // SMLU_NO_GRAPH: eager launches, no captured graphs
@@ -35,6 +37,9 @@ struct Tune {
   int host_threads = 0;       // OMP_NUM_THREADS: cap on the analysis threads (0 = not set)
 };
 Tune tune();
+// SMLU_TRAIL_NS is held at or above kTrailNsMin (no front of the recorded schedule digests reaches
+// it); kTrailNsTest is the one smaller value it accepts, for tests on oracle-sized fronts
+constexpr int64_t kTrailNsMin = 1024, kTrailNsTest = 64;
 
 
 struct PlanOptions {

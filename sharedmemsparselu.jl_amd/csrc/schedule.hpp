@@ -160,6 +160,9 @@ struct Schedule {
   // L rows below the outer block on the side stream (Launch.side in fac): launches, and the rows
   // their TRSM tasks take off the panel chain, summed over the steps
   int64_t side_launches = 0, side_rows = 0;
+  // trailing updates in tree order (SMLU_TRAIL_SPAN): the span as built, the fronts that take it,
+  // and the longest k of a K_GEMMO task
+  int64_t trail_span = 1, trail_fronts = 0, gemmo_kmax = 0;
   // statistics
   double gemm_flops = 0, gemm22_flops = 0;
   double gemm_bytes = 0;      // algorithmic bytes of the GEMM launches: A, B read, C read + written

@@ -161,7 +161,9 @@ struct Builder {
       for (auto& g : cand) kmax = std::max(kmax, g.k);
       tile = kmax <= 64 ? 65 : in.use_mfma ? 66 : 64;   // 66: the 64 tile on the matrix cores
     }
-    if (step < 0)   // F22: longest k first, so the launch's last tiles are short ones
+    // F22, and the outer trailing updates (tree order: k from one outer block to `span` of them):
+    // longest k first, so the launch's last tiles are short ones
+    if (step < 0 || kind == K_GEMMO)
       std::stable_sort(cand.begin(), cand.end(), [](const GemmRec& a, const GemmRec& b) { return a.k > b.k; });
     Launch L = launch(step < 0 ? K_GEMM22 : kind, step, S.gt.size());
     if (step < 0 && !f22_gather(cand, tile, L)) return;
@@ -171,6 +173,7 @@ struct Builder {
     for (GemmRec& g : cand) {
       if (count) S.gemm_bytes += 8.0 * ((double)g.m * g.k + (double)g.k * g.n + 2.0 * g.m * g.n);
       if (g.A.buf == kTinv.buf || g.B.buf == kTinv.buf) S.uses_tinv = true;
+      if (kind == K_GEMMO) S.gemmo_kmax = std::max<int64_t>(S.gemmo_kmax, g.k);
       g.tiles_m = (g.m + ts - 1) / ts;
       g.tile0 = tiles;
       tiles += (int64_t)g.tiles_m * ((g.n + ts - 1) / ts);
@@ -609,6 +612,7 @@ struct Builder {
       if (r.mode == 0) continue;
       bidx[s] = (int64_t)big.size();
       big.push_back(s);
+      S.trail_fronts += trail(s);
       maxsteps = std::max<int64_t>(maxsteps, (r.ns + r.nb - 1) / r.nb);
     }
     S.max_list = std::max<int64_t>(S.max_list, dist_slots + (int64_t)big.size() * spf);
@@ -880,8 +884,21 @@ struct Builder {
       const Step g = geom(s, t);
       if (g.oend == g.M) continue;   // nothing right of the block
       items.push_back(URows{s, g.ostart, g.oend, g.oend, r.ns, true});
-      rank_update(s, g.oend, g.M, g.oend, r.ns, false, g.ostart, g.oend, c1, fl1);
-      rank_update(s, g.oend, r.ns, g.oend, g.oend, true, g.ostart, g.oend, c1, fl1);   // U12 rows only
+      // L columns and U rows [k0, oend) applied to the block rows and columns [oend, e): the whole
+      // trailing part (e = ns) with the block just finished, or, in tree order, the next lowbit(j)
+      // outer blocks with the last lowbit(j) finished ones
+      int64_t k0 = g.ostart, e = r.ns;
+      if (trail(s) && g.oend < r.ns) {
+        const int64_t j = g.oend / S.ob, span = in.tn.trail_span, b = j & -j;
+        if (span > 0 && j % span == 0) {
+          k0 = (j - span) * S.ob;
+        } else {
+          k0 = (j - b) * S.ob;
+          e = std::min<int64_t>(r.ns, (j + b) * S.ob);
+        }
+      }
+      rank_update(s, g.oend, g.M, g.oend, e, false, k0, g.oend, c1, fl1);   // column strip, with the L21 rows
+      rank_update(s, g.oend, e, e, r.ns, true, k0, g.oend, c1, fl1);        // row strip and its U12 rows
     }
     urows(t, items);
     add_gemm_launch(c1, fl1, (int)t, K_GEMMO);
@@ -963,9 +980,109 @@ struct Builder {
     const SNode& r = S.hsn[s];
     const int64_t M = (int64_t)r.ns + r.nu;
     const Operand F = kStore + r.Loff, U = kStore + r.Uoff;
+    const size_t had = cand.size();
     update(cand, fl, F + k0 * M + r0, F + c0 * M + k0, F + c0 * M + r0, r1 - r0, c1 - c0, k1 - k0, M, M, M);
     const int64_t ru1 = std::min<int64_t>(r1, r.ns);   // U12 rows live above ns
     if (u12) update(cand, fl, F + k0 * M + r0, U + k0, U + r0, ru1 - r0, r.nu, k1 - k0, M, r.ns, r.ns);
+    for (size_t i = had; i < cand.size(); ++i) cand[i].front = (int32_t)s;
+  }
+
+  // ---- trailing updates in tree order -----------------------------------------------------
+  // Today's order loads, updates (k = OB) and stores block (r, c) of a front once per finished
+  // outer block, min(r, c) times.  Only the next outer block's rows and columns have to be complete
+  // when its chain starts, so after j finished blocks a qualifying front updates just the blocks
+  // with min(r, c) in [j, j + lowbit(j)), with the last lowbit(j) blocks as one k-range (the order
+  // of recursive LU; outer_block_end).  With a finite span every span-th boundary updates all that
+  // is right of it with k = span * OB instead, and the pattern restarts there.  The k-ranges a
+  // block receives tile [0, min(r, c) * OB) once, ascending, each tile one FMA per k from
+  // accumulators loaded from C: the FMA sequence of every element is today's.
+  // Same conditions as lside: one GPU, every blocked front on the diagonal-tile path.
+  bool trail(int64_t s) const {
+    const SNode& r = S.hsn[s];
+    return nranks == 1 && in.tn.trail_span != 1 && in.dominant && in.pivmode == 0 && !in.cpair && gform(s) &&
+           r.mode == 2 && r.ns >= in.tn.trail_ns;
+  }
+  // The K_GEMMO tasks of the qualifying fronts checked over the finished factor sequence.  Per
+  // front, blocks are OB x OB with one more block row (the L21 rows below ns) and one more block
+  // column (U12); done[r][c] counts the leading k-blocks applied to block (r, c).  Every task starts
+  // at that count on all blocks it covers and ends at the boundary of its launch; the first panel
+  // of outer block j finds every block with min(r, c) == j at j; the level's F22 update finds
+  // every block complete.
+  void trail_check() {
+    if (S.trail_fronts == 0) return;
+    struct Fr {
+      int64_t nB = 0;              // outer blocks; row / column nB: L21 / U12
+      std::vector<int32_t> done;   // (nB + 1) x (nB + 1)
+    };
+    std::unordered_map<int32_t, Fr> fr;
+    auto front = [&](int32_t s) -> Fr& {
+      Fr& f = fr[s];
+      if (f.done.empty()) {
+        f.nB = (S.hsn[s].ns + S.ob - 1) / S.ob;
+        f.done.assign((size_t)((f.nB + 1) * (f.nB + 1)), 0);
+      }
+      return f;
+    };
+    const char* const bad = "internal: a trailing update out of tree order";
+    for (const Launch& L : S.fac) {
+      if (L.kind == K_GEMMO) {
+        for (int64_t i = L.off; i < L.off + L.cnt; ++i) {
+          const GemmRec& g = S.gt[i];
+          if (g.front < 0 || !trail(g.front)) continue;
+          const SNode& r = S.hsn[g.front];
+          Fr& f = front(g.front);
+          const int64_t ns = r.ns, M = ns + r.nu, ob = S.ob;
+          const int64_t a = g.A.off - r.Loff, c = g.C.off - r.Loff, cu = g.C.off - r.Uoff;
+          const bool u12 = !(c >= 0 && c < M * ns);
+          if (g.A.buf != kStore.buf || g.B.buf != kStore.buf || g.C.buf != kStore.buf || a < 0 || a >= M * ns ||
+              g.lda != M || (u12 && (r.nu == 0 || cu < 0 || cu >= ns * r.nu)))
+            return fail(kSchedErrState, bad);
+          const int64_t k0 = a / M, k1 = k0 + g.k, r0 = a % M, r1 = r0 + g.m;
+          // L-panel columns [c0, c1), or all of U12 (block column nB)
+          const int64_t c0 = u12 ? ns : c / M, c1 = u12 ? M : c0 + g.n;
+          const int64_t ld = u12 ? ns : M, crow = u12 ? cu % ns : c % M, ccol = u12 ? cu / ns : 0;
+          // operands: C and B in the same columns, C in A's rows, B in A's k-range; rows and
+          // columns from a block's start to a block's end (ns and M end the last ones)
+          const bool ok = g.ldc == ld && g.ldb == ld && crow == r0 && ccol == 0 && (!u12 || g.n == r.nu) &&
+                          g.B.off == (u12 ? r.Uoff : r.Loff + c0 * M) + k0 && k0 % ob == 0 && k1 % ob == 0 &&
+                          k1 == geom(g.front, L.step).oend && k1 < ns && r0 % ob == 0 && r0 >= k1 && r0 < ns &&
+                          (r1 == M || (r1 <= ns && (r1 % ob == 0 || r1 == ns))) && (!u12 || r1 <= ns) &&
+                          (u12 || (c0 % ob == 0 && c0 >= k1 && c1 <= ns && (c1 % ob == 0 || c1 == ns)));
+          if (!ok) return fail(kSchedErrState, bad);
+          const int64_t br1 = r1 > ns ? f.nB + 1 : (r1 + ob - 1) / ob;   // block rows [r0 / ob, br1)
+          const int64_t bc0 = u12 ? f.nB : c0 / ob, bc1 = u12 ? f.nB + 1 : (c1 + ob - 1) / ob;
+          for (int64_t br = r0 / ob; br < br1; ++br)
+            for (int64_t bc = bc0; bc < bc1; ++bc) {
+              int32_t& d = f.done[(size_t)(br * (f.nB + 1) + bc)];
+              if (d != k0 / ob || k1 / ob > std::min(br, bc)) return fail(kSchedErrState, bad);
+              d = (int32_t)(k1 / ob);
+            }
+        }
+      } else if (L.kind == K_PANEL) {
+        for (int64_t i = L.off; i < L.off + 2 * L.cnt; i += 2) {
+          const int32_t s = S.ilist[i];
+          if (!trail(s)) continue;
+          const Step g = geom(s, L.step);
+          if (g.kb != g.ostart) continue;
+          const Fr& f = front(s);
+          const int64_t j = g.ostart / S.ob;
+          for (int64_t q = j; q < f.nB + (S.hsn[s].nu > 0); ++q)   // with the L21 rows and U12
+            if (f.done[(size_t)(q * (f.nB + 1) + j)] != j || f.done[(size_t)(j * (f.nB + 1) + q)] != j)
+              return fail(kSchedErrState, "internal: an outer block starts before its trailing updates are complete");
+        }
+      } else if (L.kind == K_GEMM22) {
+        for (int64_t i = L.off; i < L.off + L.cnt; ++i) {
+          const int32_t s = S.gt[i].front;
+          if (s < 0 || !trail(s)) continue;
+          const Fr& f = front(s);
+          for (int64_t br = 0; br <= f.nB; ++br)
+            for (int64_t bc = 0; bc <= f.nB; ++bc)
+              if (br + bc < 2 * f.nB && f.done[(size_t)(br * (f.nB + 1) + bc)] != std::min(br, bc))
+                return fail(kSchedErrState, "internal: an F22 update before the front's trailing updates are complete");
+          fr.erase(s);
+        }
+      }
+    }
   }
 
   // ---- the shared front's pivot-block chain (multi-GPU) -----------------------------------
@@ -1553,6 +1670,7 @@ struct Builder {
     // GEMM-form TRSM (k_tri_inv + GEMM tasks) needs the growth epilogue of the MFMA/64 tiles
     // (the 32-wide panels keep k_step_trsm: measured best)
     S.trsm_gemm = in.use_mfma;
+    S.trail_span = in.tn.trail_span;
     nodes();
     group_entries();
     levels();
@@ -1568,6 +1686,7 @@ struct Builder {
       lvl_end.push_back(S.fac.size());
     }
     if (err.empty()) lside_check();
+    if (err.empty()) trail_check();
     for (int l = 0; l < P.nlevels && err.empty(); ++l) {
       solve_level(l);
       for (const int32_t t : dfront[l]) shared_forward(t);

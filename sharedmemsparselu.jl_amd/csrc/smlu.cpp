@@ -318,6 +318,9 @@ double smlu_stat(const smlu_handle* h, const char* key) {
   if (k == "gemm128_launches") return (double)h->sch.gemm128_launches;
   if (k == "side_launches") return (double)h->sch.side_launches;
   if (k == "side_rows") return (double)h->sch.side_rows;
+  if (k == "trail_span") return (double)h->sch.trail_span;
+  if (k == "trail_fronts") return (double)h->sch.trail_fronts;
+  if (k == "gemmo_kmax") return (double)h->sch.gemmo_kmax;
   if (k == "vendor_calls") return 0.0;   // no vendor GEMM path (round 5)
   if (k.rfind("ms_", 0) == 0) {
     std::string name = k.substr(3);

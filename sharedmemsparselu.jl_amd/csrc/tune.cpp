@@ -17,6 +17,15 @@ Tune tune() {
     if (const char* e = std::getenv("SMLU_F22_GATHER_NU")) v.f22_gather_nu = std::atoll(e);
     if (const char* e = std::getenv("SMLU_F22_GATHER_CH")) v.f22_gather_ch = std::atoll(e);
     if (const char* e = std::getenv("SMLU_LSIDE_MIN")) v.lside_min = std::max<long long>(0, std::atoll(e));
+    if (const char* e = std::getenv("SMLU_TRAIL_SPAN")) {   // 0, or rounded down to a power of two
+      const int s = std::max(0, std::atoi(e));
+      v.trail_span = s;
+      while (v.trail_span & (v.trail_span - 1)) v.trail_span &= v.trail_span - 1;
+    }
+    if (const char* e = std::getenv("SMLU_TRAIL_NS")) {   // 64: the tests' lower bound
+      const long long r = std::atoll(e);
+      v.trail_ns = r == kTrailNsTest ? r : std::max<long long>(kTrailNsMin, r);
+    }
     if (const char* e = std::getenv("SMLU_SWEEP_SPIN")) v.sweep_spin = std::atoi(e);
     if (const char* e = std::getenv("SMLU_SOLVE_STEPS")) v.solve_steps = std::atoi(e) == 1;
     v.no_graph = std::getenv("SMLU_NO_GRAPH") != nullptr;

@@ -32,6 +32,13 @@ int main(int argc, char** argv) {
   sv.push_back({18000, 192, 64});
   sv.push_back({18000, 64, 64});
   sv.push_back({3072, 3072, 384});   // no edge tile
+  // the strips of the tree-ordered trailing updates (SMLU_TRAIL_SPAN): one outer block of columns or
+  // rows of the root front at k = 1, 2, 4, 8, 16 outer blocks, four blocks at k = 4, and a deep square
+  for (int k : {384, 768, 1536, 3072, 6144}) sv.push_back({18000, 384, k});
+  for (int k : {384, 768, 1536, 3072, 6144}) sv.push_back({384, 18000, k});
+  sv.push_back({18000, 1536, 1536});
+  sv.push_back({1536, 18000, 1536});
+  sv.push_back({16384, 384, 8192});
   if (argc > 1) {   // shapes from the command line: m,n,k ...
     sv.clear();
     for (int a = 1; a < argc; ++a) {   // m,n,k or m,n,k,lda,ldb,ldc
