@@ -305,6 +305,71 @@ int smlu_solve_gmres(smlu_handle* h, int op, const double* nzval, const double* 
 int smlu_solve_gmres_device(smlu_handle* h, int op, const double* d_nzval, const double* d_b, double* d_x,
                             const smlu_gmres_opts* opts, smlu_gmres_info* info);
 
+/* Low-rank updates: solve op(A + U V^T) x = b from the handle's current factors of A, U and V dense
+ * n x k with k <= SMLU_LOWRANK_MAX, by the Sherman-Morrison-Woodbury identity
+ *   (A + U V^T)^-1 b = y0 - Y C^-1 (V^T y0),   y0 = A^-1 b,   Y = A^-1 U,   C = I + V^T Y  (k x k).
+ * For a matrix that changed by any amount but only in a few columns or rows (a boundary condition
+ * that flips, a few dense constraint rows kept out of the pattern, a bordered system), where GMRES on
+ * the stale factors converges slowly and the only other exact route is a refactor (what MUMPS and
+ * PARDISO users do by hand on the host; not in the reference).  All n-vectors stay on the device.
+ *
+ * smlu_lowrank_set[_device](h, k, U, ldu, V, ldv, info) installs the update: column j of U at
+ * U + j*ldu, of V at V + j*ldv, ldu, ldv >= n.  U and V are copied into the handle, Y = A^-1 U is
+ * computed by the plain factor solve in batches of 16 columns (never refined, whatever
+ * smlu_opts.refine says, as smlu_rcond), C is formed and factored on the device by LU with partial
+ * pivoting and its explicit inverse kept; the host reads one 64-byte record.  k = 0 is
+ * smlu_lowrank_clear.  info (may be NULL): k, solves (factor solve passes run), rcond_c (1-norm
+ * reciprocal condition of C from its explicit inverse), pivot_min (min |u_ii| of C's LU), gram_max
+ * (max |(V^T Y)_ij|); the other fields are 0 / -1.  SMLU_ERR_ARG: NULL handle, k < 0,
+ * k > SMLU_LOWRANK_MAX, a NULL pointer with k > 0, a leading dimension below n; a call refused for
+ * its arguments or for the handle's state leaves an installed update as it was.  SMLU_SINGULAR
+ * (positive): a pivot of C exactly zero, i.e. A + U V^T is singular as far as the factors can tell, or
+ * a non-finite entry of C; then nothing is installed -- an earlier update is dropped as well -- and
+ * the handle stays usable.  The _device form reads U and V after the caller's stream
+ * (smlu_set_stream).  The handle stays as it was: a later smlu_solve* is bitwise what it was before,
+ * and the determinant and rcond caches are untouched.  Every refactor (smlu_refactor*, _csc, _z*)
+ * drops the installed update, because the factors are then of another matrix; the buffers are kept.
+ *
+ * smlu_solve_lowrank[_device](h, op, max_steps, b, x, info) solves op(A + U V^T) x = b; x == b allowed.
+ *   op         SMLU_OP_N: the identity above.  SMLU_OP_T or SMLU_OP_H (a real handle: the same):
+ *              op(A + U V^T) = A^T + V U^T, so y0 = A^-T b, x = y0 - Yt C^-T (U^T y0) with
+ *              Yt = A^-T V, computed on the first transposed solve after a set (batches of 16) and
+ *              kept; the stored C^-1 is used transposed.  Anything else: SMLU_ERR_ARG.
+ *   max_steps  iterative refinement on the updated system: 0 none, m > 0 up to m corrections, -1 up
+ *              to 3 (the identity is less stable than a plain solve, so refining is the default);
+ *              below -1: SMLU_ERR_ARG.  A step computes r = b - op(A) x - U (V^T x) (T: V (U^T x)) and
+ *              the componentwise backward error max_i |r_i| / (|op(A)||x| + |U| (|V|^T |x|) + |b|)_i on
+ *              the device, and stops as the refined solve does: when berr <= 2^-51 (stop 1), when it
+ *              fails to halve (stop 2), or at the step limit (stop 3); otherwise the correction is
+ *              solved through the same identity and added.
+ *   info       may be NULL: k (the rank in force), steps (corrections made), stop (as
+ *              smlu_refine_info), solves (factor solves run: 1 + steps; the passes that compute Yt
+ *              are not counted), berr and resid (max |r_i|) as last measured, -1 if never.
+ * With no update installed it is the plain solve of that direction, refined by the same rule (k = 0).
+ * Two identical sequences of calls are bitwise equal, and so are the host and device forms.
+ * SMLU_ERR_STATE (both calls): no numeric factorization (none yet, or a singular one), a partitioned
+ * handle (smlu_dist_*), or a ComplexF64 handle.  Buffers (U, V, Y, Yt after the first transposed solve:
+ * k columns of leading dimension n rounded up to even; three n-vectors; the partials) belong to the
+ * handle: allocated on first use, grown with k, freed with it; SMLU_ERR_ALLOC when they do not fit
+ * (128^3 with k = 32: four n x 32 buffers, 2.1 GB).  smlu_stat: "lowrank_k" (rank in force),
+ * "lowrank_solves", "lowrank_set_ms_last", "lowrank_ms_last" (the last call); the factor solves count
+ * in "solve_passes" / "solve_trans_passes", one per batch of up to 16 columns, and "solve_ms_last"
+ * holds the last of them, as after smlu_rcond. */
+#define SMLU_LOWRANK_MAX 32
+typedef struct smlu_lowrank_info {
+  int32_t k, steps, stop, solves;        /* rank in force; corrections made; stop as smlu_refine_info; factor solves run */
+  double berr, resid;                    /* last ones measured (-1: nothing measured) */
+  double rcond_c, pivot_min, gram_max;   /* of C: 1-norm rcond from its explicit inverse; min |u_ii| of its LU; max |(V^T Y)_ij| */
+} smlu_lowrank_info;
+int smlu_lowrank_set(smlu_handle* h, int32_t k, const double* U, int64_t ldu, const double* V, int64_t ldv,
+                     smlu_lowrank_info* info);
+int smlu_lowrank_set_device(smlu_handle* h, int32_t k, const double* d_U, int64_t ldu, const double* d_V, int64_t ldv,
+                            smlu_lowrank_info* info);
+int smlu_lowrank_clear(smlu_handle* h);
+int smlu_solve_lowrank(smlu_handle* h, int op, int max_steps, const double* b, double* x, smlu_lowrank_info* info);
+int smlu_solve_lowrank_device(smlu_handle* h, int op, int max_steps, const double* d_b, double* d_x,
+                              smlu_lowrank_info* info);
+
 /* ParallelSparseLU(A::SparseMatrixCSC{Float64,Int32}) — Int32 index arrays;
  * converted to the Int64 path on the host. */
 int smlu_create_i32(int64_t n, const int32_t* colptr, const int32_t* rowval, const double* nzval,
@@ -404,7 +469,8 @@ int64_t     smlu_last_error_col(const smlu_handle* h);      /* column of A (the 
  * "growth_max","dense_flops","gemm_flops","ms_gemm","ms_panel","ms_trsm","ms_assemble",
  * "ms_small","ms_solve","solve_passes","solve_trans_passes","rcond_solves","rcond_solves_fwd","rcond_solves_adj",
  * "rcond_iters","logabsdet_evals","gmres_iters","gmres_cycles","gmres_solves","gmres_ms_last",
- * "refine_steps","refine_berr","refine_residual","refine_batch_residuals".
+ * "refine_steps","refine_berr","refine_residual","refine_batch_residuals",
+ * "lowrank_k","lowrank_solves","lowrank_set_ms_last","lowrank_ms_last".
  * Returns NaN for an unknown key. */
 double smlu_stat(const smlu_handle* h, const char* key);
 

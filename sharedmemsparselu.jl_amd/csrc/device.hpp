@@ -134,6 +134,12 @@ constexpr int kKryMaxRestart = 32;
 constexpr int kKryPartStride = kKryMaxRestart + 2;
 constexpr int kKryStateWords = 1 + 2 * kKryMaxRestart + kKryMaxRestart * kKryMaxRestart + 2 * kKryMaxRestart +
                                (kKryMaxRestart + 1) + kKryMaxRestart;
+// kernels_lowrank.hip: the largest rank of an update (SMLU_LOWRANK_MAX), the doubles of one
+// workgroup's partial (the dots, the dots of absolute values, max |r| and the backward error) and of
+// the device state (C^-1, C, max |G_ij| and a spare)
+constexpr int kLrMax = 32;
+constexpr int kLrPartStride = 2 * kLrMax + 2;
+constexpr int kLrStateWords = 2 * kLrMax * kLrMax + 2;
 #ifndef SMLU_SWEEP_WK
 #define SMLU_SWEEP_WK 4
 #endif

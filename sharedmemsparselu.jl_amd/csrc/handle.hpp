@@ -5,7 +5,7 @@
 //   solve.cpp     (solves, refinement, chunked layout)     export.cpp  (factor export, pattern hand-over)
 //   complex.cpp   (ComplexF64 handles)                     dist.cpp    (RCCL, partitioned handles)
 //   smlu.cpp      (create / destroy / stats / plan API)    diag.cpp    (determinant, condition estimate)
-//   krylov.cpp    (GMRES preconditioned by the factors)
+//   krylov.cpp    (GMRES preconditioned by the factors)        lowrank.cpp (low-rank updates of the solve)
 #pragma once
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -132,6 +132,15 @@ hipError_t launch_residual_t_batch(hipStream_t, int64_t, const int64_t*, const i
                                    int64_t, const double*, double*, double*, int, int, const int32_t*);
 hipError_t launch_axpy_cols(hipStream_t, int64_t, const double*, double*, int64_t, int, const int32_t*);
 hipError_t launch_refine_record(hipStream_t, const double*, long long*, long long);
+// kernels_lowrank.hip: low-rank updates (the capacitance matrix and the residual end in the 64-byte record rec)
+hipError_t launch_lr_stage(hipStream_t, int64_t, int64_t, int, const double*, int64_t, double*);
+hipError_t launch_lr_capacitance(hipStream_t, int64_t, int64_t, int, const double*, const double*, double*, void*,
+                                 long long*, long long);
+hipError_t launch_lr_correct(hipStream_t, bool, int64_t, int64_t, int, const double*, const double*, const void*, double*,
+                             double*);
+hipError_t launch_lr_resid(hipStream_t, bool, int64_t, int64_t, int, const int64_t*, const int32_t*, const int32_t*,
+                           const int64_t*, const int32_t*, const double*, const double*, const double*, const double*,
+                           const double*, double*, double*, long long*, long long);
 }  // namespace smlu
 
 using namespace smlu;
@@ -339,6 +348,20 @@ struct smlu_handle {
   long long kry_seq = 0;
   int64_t gmres_iters = 0, gmres_cycles = 0, gmres_solves = 0;   // of the last call
   double gmres_ms = 0;
+  // low-rank update of the solve (lowrank.cpp): buffers allocated on first use and grown with the rank;
+  // lr_cols columns of U, V, Y (and lr_cols_t of Yt) of leading dimension n rounded up to even.  The
+  // update belongs to the factorization it was installed on: in force while lr_version == nfactor.
+  DBuf<double> lr_U, lr_V, lr_Y, lr_Yt, lr_b, lr_x, lr_r, lr_part, lr_gpart, lr_state;
+  DBuf<long long> lr_rec;
+  int lr_cols = 0, lr_cols_t = 0;
+  bool lr_ready = false;    // the vectors, partials, state and record are all allocated and cleared
+  bool lr_have_t = false;   // Yt = A^-T V holds the installed update's columns
+  int lr_k = 0;             // rank installed (0: none)
+  int64_t lr_version = -1;
+  long long lr_seq = 0;
+  int64_t lowrank_solves = 0;   // factor solves of the last smlu_lowrank_set* / smlu_solve_lowrank*
+  double lowrank_set_ms = 0, lowrank_ms = 0;
+  int lowrank_k() const { return lr_version == nfactor ? lr_k : 0; }
   ~smlu_handle() { release_all(); }
   void release_buffers() {
     if (stream) (void)hipSetDevice(device);
@@ -371,6 +394,11 @@ struct smlu_handle {
     kry_rec.free();
     kry_cols = 0;
     kry_ready = false;
+    DBuf<double>* lr[] = {&lr_U, &lr_V, &lr_Y, &lr_Yt, &lr_b, &lr_x, &lr_r, &lr_part, &lr_gpart, &lr_state};
+    for (auto* b : lr) b->free();
+    lr_rec.free();
+    lr_cols = lr_cols_t = lr_k = 0;
+    lr_ready = lr_have_t = false;
     xtasks.free();
     aents.free();
     ftiles.free();

@@ -262,6 +262,11 @@ double smlu_stat(const smlu_handle* h, const char* key) {
   if (k == "gmres_cycles") return (double)h->gmres_cycles;
   if (k == "gmres_solves") return (double)h->gmres_solves;
   if (k == "gmres_ms_last") return h->gmres_ms;
+  // low-rank update (lowrank.cpp): the rank in force; factor solves and wall time of the last set / solve
+  if (k == "lowrank_k") return (double)h->lowrank_k();
+  if (k == "lowrank_solves") return (double)h->lowrank_solves;
+  if (k == "lowrank_set_ms_last") return h->lowrank_set_ms;
+  if (k == "lowrank_ms_last") return h->lowrank_ms;
   if (k == "sweep_status") {     // the device flag itself (cleared whenever a solve reports it)
     int32_t v = 0;
     if (h->sstatus.p && hipMemcpy(&v, h->sstatus.p, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;

@@ -4,6 +4,7 @@
 module SharedMemSparseLU
 
 export ParallelSparseLU, cleanup_ParallelSparseLU!, allocate_shared, gmres!, ldiv_refined!
+export lowrank!, lowrank_clear!, ldiv_lowrank!
 
 using LinearAlgebra, SparseArrays, Libdl
 import LinearAlgebra: ldiv!, lu!
@@ -279,6 +280,53 @@ function gmres!(x::AbstractVector, F::ParallelSparseLU{Float64}, A::Union{Sparse
     xx === x || copyto!(x, xx)
     return x, info
 end
+
+# lowrank!(F, U, V): install the update A + U V' on the factors F already holds, U and V dense n x k,
+# k <= 32 (smlu_lowrank_set; the Sherman-Morrison-Woodbury identity): for a matrix that changed by any
+# amount in a few columns or rows, or a few dense rows or columns kept out of the pattern.  Returns
+# info (rcond_c, pivot_min and gram_max of the capacitance matrix); a singular one (status 1) throws
+# SingularException(0) and installs nothing.  lu!(F, .) drops the update.
+# ldiv_lowrank!(x, F, b; steps=-1), also on transpose(F) and F': solve (A + U V') x = b, refined on the
+# updated system (steps = -1: up to 3 corrections; 0: none).  Returns (x, info).
+# LowrankInfo must match the header's low-rank record field for field.
+mutable struct LowrankInfo
+    k::Int32; steps::Int32; stop::Int32; solves::Int32
+    berr::Float64; resid::Float64; rcond_c::Float64; pivot_min::Float64; gram_max::Float64
+end
+LowrankInfo() = LowrankInfo(0, 0, 0, 0, -1.0, -1.0, -1.0, -1.0, -1.0)
+function lowrank!(F::ParallelSparseLU{Float64}, U::AbstractVecOrMat, V::AbstractVecOrMat)
+    size(U) == size(V) || throw(DimensionMismatch("`U` has size $(size(U)), `V` has size $(size(V))"))
+    size(U, 1) == F.n || throw(DimensionMismatch("`U` does not have same size as F: size(U, 1)=$(size(U, 1)), F.n=$(F.n)"))
+    size(U, 2) <= 32 || throw(ArgumentError("lowrank!: the rank of an update is at most 32, got $(size(U, 2))"))
+    uu = U isa Array{Float64} ? U : Array{Float64}(U)
+    vv = V isa Array{Float64} ? V : Array{Float64}(V)
+    info = LowrankInfo()
+    rc = ccall((:smlu_lowrank_set, libsmlu), Int32,
+               (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ref{LowrankInfo}),
+               F.handle, Int32(size(U, 2)), uu, Int64(F.n), vv, Int64(F.n), info)
+    rc < 0 && check(rc, F.handle)
+    rc == 1 && throw(SingularException(0))
+    return info
+end
+lowrank_clear!(F::ParallelSparseLU) = (check(ccall((:smlu_lowrank_clear, libsmlu), Int32, (Ptr{Cvoid},), F.handle), F.handle); nothing)
+function _ldiv_lowrank!(op::Int32, x::AbstractVector, F::ParallelSparseLU{Float64}, b::AbstractVector, steps::Integer)
+    length(x) == length(b) == F.n || throw(DimensionMismatch("x, b and F sizes differ"))
+    steps >= -1 || throw(ArgumentError("ldiv_lowrank!: steps must be -1, 0 or a step limit, got $steps"))
+    bb = b isa Vector{Float64} ? b : Vector{Float64}(b)
+    xx = x isa Vector{Float64} ? x : similar(bb)
+    info = LowrankInfo()
+    check(ccall((:smlu_solve_lowrank, libsmlu), Int32,
+                (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ref{LowrankInfo}),
+                F.handle, op, Int32(steps), bb, xx, info), F.handle)
+    xx === x || copyto!(x, xx)
+    return x, info
+end
+ldiv_lowrank!(x::AbstractVector, F::ParallelSparseLU, b::AbstractVector; steps::Integer=-1) =
+    _ldiv_lowrank!(Int32(0), x, F, b, steps)
+ldiv_lowrank!(x::AbstractVector, W::TransposedLU, b::AbstractVector; steps::Integer=-1) =
+    _ldiv_lowrank!(Int32(1), x, W.parent, b, steps)
+ldiv_lowrank!(x::AbstractVector, W::AdjointLU, b::AbstractVector; steps::Integer=-1) =
+    _ldiv_lowrank!(Int32(2), x, W.parent, b, steps)
 
 function _trisolve!(upper::Bool, F::ParallelSparseLU{Tf}, x::AbstractVector) where {Tf}
     xx = x isa Vector{Tf} ? x : Vector{Tf}(x)

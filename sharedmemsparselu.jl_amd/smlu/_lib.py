@@ -76,6 +76,15 @@ class SmluRefineInfo(ctypes.Structure):
     _fields_ = [("steps", i32), ("stop", i32), ("berr", f64), ("resid", f64)]
 
 
+SMLU_LOWRANK_MAX = 32
+
+
+class SmluLowrankInfo(ctypes.Structure):
+    """smlu_lowrank_info: what smlu_lowrank_set* and smlu_solve_lowrank* report."""
+    _fields_ = [("k", i32), ("steps", i32), ("stop", i32), ("solves", i32),
+                ("berr", f64), ("resid", f64), ("rcond_c", f64), ("pivot_min", f64), ("gram_max", f64)]
+
+
 # exported symbols and their signatures (restype, argtypes); the CPU test-suite checks that
 # every function declared in include/smlu.h is present here and in the .so
 SIGNATURES = {
@@ -109,6 +118,11 @@ SIGNATURES = {
     "smlu_solve_gmres": (i32, [vp, i32, vp, vp, vp, ctypes.POINTER(SmluGmresOpts), ctypes.POINTER(SmluGmresInfo)]),
     "smlu_solve_gmres_device": (i32, [vp, i32, vp, vp, vp, ctypes.POINTER(SmluGmresOpts),
                                       ctypes.POINTER(SmluGmresInfo)]),
+    "smlu_lowrank_set": (i32, [vp, i32, vp, i64, vp, i64, ctypes.POINTER(SmluLowrankInfo)]),
+    "smlu_lowrank_set_device": (i32, [vp, i32, vp, i64, vp, i64, ctypes.POINTER(SmluLowrankInfo)]),
+    "smlu_lowrank_clear": (i32, [vp]),
+    "smlu_solve_lowrank": (i32, [vp, i32, i32, vp, vp, ctypes.POINTER(SmluLowrankInfo)]),
+    "smlu_solve_lowrank_device": (i32, [vp, i32, i32, vp, vp, ctypes.POINTER(SmluLowrankInfo)]),
     "smlu_create_i32": (i32, [i64, vp, vp, vp, ctypes.POINTER(SmluOpts), ctypes.POINTER(vp)]),
     "smlu_create_z": (i32, [i64, vp, vp, vp, ctypes.POINTER(SmluOpts), ctypes.POINTER(vp)]),
     "smlu_refactor_z": (i32, [vp, vp]),

@@ -12,6 +12,8 @@ lsolve!(F, x), rsolve!(F, x)        lsolve_(F, x), rsolve_(F, x)  :349-392
 logabsdet(F), det(F), logdet(F)     F.logabsdet() F.det() F.logdet()  (not in the reference)
 cond(F, 1), cond(F, Inf)            F.condest("1"|"inf"), F.rcond()   (not in the reference)
 gmres!(x, F, A, b)                  F.gmres(b, values=A)          (not in the reference)
+lowrank!(F, U, V)                   F.lowrank_set(U, V)           (not in the reference)
+ldiv_lowrank!(x, F, b)              F.solve_lowrank(b)            (not in the reference)
 F.L F.U F.p F.q F.Rs                F.L F.U F.p F.q F.Rs          :45-52 (0-based here)
 cleanup_ParallelSparseLU!(F)        cleanup_ParallelSparseLU_(F)  :31 (exported, undefined there)
 DimensionMismatch                   DimensionMismatch             :288-290
@@ -123,6 +125,27 @@ def _device_f64(name, t, size):
 def _gmres_info(rc, ci):
     return GmresInfo(bool(ci.converged), ci.iters, ci.cycles, ci.solves, ci.relres, ci.relres_est, ci.berr,
                      ci.bnorm, rc)
+
+
+LowrankInfo = collections.namedtuple(
+    "LowrankInfo", "k steps stop solves berr resid rcond_c pivot_min gram_max status")
+LowrankInfo.__doc__ = """What smlu_lowrank_set* and smlu_solve_lowrank* report: k (rank in force), steps
+(corrections made), stop (0 not refined, 1 berr <= 2^-51, 2 berr did not halve, 3 step limit), solves
+(factor solves run), berr and resid (last measured, -1 if never), rcond_c, pivot_min and gram_max (of the
+capacitance matrix, from a set; -1 from a solve), status (the C return code: 0 or SMLU_SINGULAR)."""
+
+
+def _lowrank_info(rc, ci):
+    return LowrankInfo(ci.k, ci.steps, ci.stop, ci.solves, ci.berr, ci.resid, ci.rcond_c, ci.pivot_min,
+                       ci.gram_max, rc)
+
+
+def _lowrank_steps(steps):
+    """max_steps of smlu_solve_lowrank*: an integer >= -1, raised as ValueError before any handle is
+    looked at."""
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < -1:
+        raise ValueError(f"steps must be an integer >= -1, got {steps!r}")
+    return int(steps)
 
 
 def _refine_steps(steps):
@@ -532,6 +555,120 @@ class ParallelSparseLU:
             rc = _check(C.lib().smlu_solve_gmres_device(self._h, op, pv, ctypes.c_void_p(pb), ctypes.c_void_p(px),
                                                         ctypes.byref(o), ctypes.byref(ci)), self._h)
         return _gmres_info(rc, ci)
+
+    # ---- low-rank updates of the solve (smlu_lowrank_*, smlu_solve_lowrank*) ----
+    def _lowrank_real(self, who):
+        if self.is_complex:   # out of scope, as in the library (SMLU_ERR_STATE)
+            e = SmluError(f"libsmlu error {C.SMLU_ERR_STATE}: {who}: ComplexF64 handles are not supported")
+            e.code = C.SMLU_ERR_STATE
+            raise e
+
+    def lowrank_set(self, U, V):
+        """Install the update A + U V^T on the current factors (smlu_lowrank_set): U and V are n x k
+        arrays (or n-vectors, k = 1), k <= 32.  Y = A^-1 U, C = I + V^T Y and C^-1 are computed on the
+        GPU.  Returns LowrankInfo (k, solves, rcond_c, pivot_min, gram_max; status SMLU_OK, or
+        SMLU_SINGULAR when C is singular or not finite: then nothing is installed).  Every refactor
+        drops the update.  k = 0 (n x 0 arrays) clears it."""
+        self._lowrank_real("lowrank_set")
+        U = np.asarray(U, dtype=np.float64)
+        V = np.asarray(V, dtype=np.float64)
+        if U.ndim == 1:
+            U = U[:, None]
+        if V.ndim == 1:
+            V = V[:, None]
+        if U.ndim != 2 or V.ndim != 2 or U.shape != V.shape or U.shape[0] != self.n:
+            raise DimensionMismatch(f"U has shape {U.shape}, V has shape {V.shape}, expected two ({self.n}, k) arrays")
+        k = U.shape[1]
+        if k > C.SMLU_LOWRANK_MAX:
+            raise ValueError(f"the rank of an update is at most {C.SMLU_LOWRANK_MAX}, got {k}")
+        Uf, Vf = np.asfortranarray(U), np.asfortranarray(V)     # column j at j * n
+        ci = C.SmluLowrankInfo()
+        rc = _check(C.lib().smlu_lowrank_set(self._h, k, C.ptr(Uf) if k else None, self.n, C.ptr(Vf) if k else None,
+                                             self.n, ctypes.byref(ci)), self._h)
+        return _lowrank_info(rc, ci)
+
+    def lowrank_set_device(self, d_U, d_V):
+        """lowrank_set with U and V on the device: (k, n) contiguous float64 torch tensors (row j is
+        column j, as in solve_multi_device).  Ordered after the stream that produced d_U."""
+        self._lowrank_real("lowrank_set_device")
+        if tuple(d_U.shape) != tuple(d_V.shape) or d_U.dim() != 2 or d_U.shape[1] != self.n:
+            raise DimensionMismatch(f"U has shape {tuple(d_U.shape)}, V has shape {tuple(d_V.shape)}, n={self.n}")
+        k = int(d_U.shape[0])
+        if k > C.SMLU_LOWRANK_MAX:
+            raise ValueError(f"the rank of an update is at most {C.SMLU_LOWRANK_MAX}, got {k}")
+        for name, t in (("d_U", d_U), ("d_V", d_V)):
+            _device_f64(name, t, k * self.n)
+        ci = C.SmluLowrankInfo()
+        with C.caller_stream(self._h, d_U):
+            rc = _check(C.lib().smlu_lowrank_set_device(self._h, k, ctypes.c_void_p(d_U.data_ptr()), self.n,
+                                                        ctypes.c_void_p(d_V.data_ptr()), self.n, ctypes.byref(ci)),
+                        self._h)
+        return _lowrank_info(rc, ci)
+
+    def lowrank_clear(self):
+        """Drop the installed update (smlu_lowrank_clear); the buffers are kept."""
+        _check(C.lib().smlu_lowrank_clear(self._h), self._h)
+
+    def update_columns(self, cols, A_new, A):
+        """The update that replaces the columns `cols` of A, the matrix F holds the factors of, by those
+        of A_new: U[:, t] = A_new[:, cols[t]] - A[:, cols[t]], V[:, t] = e_cols[t], then lowrank_set.
+        Outside `cols` the two matrices must be equal, pattern and values; the changed columns may have
+        any pattern (a dense column costs no fill).  Returns lowrank_set's info."""
+        A, A_new = _csc(A), _csc(A_new)
+        cols = np.asarray(cols, dtype=np.int64).ravel()
+        if A.shape != (self.m, self.n) or A_new.shape != A.shape:
+            raise DimensionMismatch(f"A has shape {A.shape}, A_new has shape {A_new.shape}, F.n={self.n}")
+        if cols.size and (cols.min() < 0 or cols.max() >= self.n or np.unique(cols).size != cols.size):
+            raise ValueError("update_columns: `cols` must be distinct column indices of A")
+        keep = np.ones(self.n, bool)
+        keep[cols] = False
+        rest, rest_new = A[:, keep], A_new[:, keep]
+        if not (np.array_equal(rest.indptr, rest_new.indptr) and np.array_equal(rest.indices, rest_new.indices)
+                and np.array_equal(rest.data, rest_new.data)):
+            raise ValueError("update_columns: A_new must equal A, pattern and values, outside `cols`")
+        U = np.asfortranarray((A_new[:, cols] - A[:, cols]).toarray())
+        V = np.zeros((self.n, cols.size), order="F")
+        V[cols, np.arange(cols.size)] = 1.0
+        return self.lowrank_set(U, V)
+
+    def solve_lowrank(self, b, trans="N", steps=-1, x=None):
+        """Solve op(A + U V^T) x = b with the installed update (smlu_solve_lowrank); trans as ldiv_.
+        steps: refinement on the updated system, -1 up to 3 corrections (the default), 0 none, m > 0
+        up to m.  Returns (x, info); x is written into the given array when one is passed (it may be
+        b).  With no update installed it is the plain solve of that direction (info.k == 0)."""
+        op = _op(trans)
+        steps = _lowrank_steps(steps)
+        self._lowrank_real("solve_lowrank")
+        if len(b) != self.n:
+            raise DimensionMismatch(f"`b` does not have same size as F: length(b)={len(b)}, F.n={self.n}")
+        bb = np.ascontiguousarray(b, dtype=np.float64)
+        if x is None:
+            x = np.empty(self.n)
+        elif len(x) != self.n:
+            raise DimensionMismatch(f"`x` does not have same size as F: length(x)={len(x)}, F.n={self.n}")
+        xx = x if (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.flags.c_contiguous) \
+            else np.empty(self.n)
+        ci = C.SmluLowrankInfo()
+        rc = _check(C.lib().smlu_solve_lowrank(self._h, op, steps, C.ptr(bb), C.ptr(xx), ctypes.byref(ci)), self._h)
+        if xx is not x:
+            x[:] = xx
+        return x, _lowrank_info(rc, ci)
+
+    def solve_lowrank_device(self, d_x, d_b, trans="N", steps=-1):
+        """solve_lowrank on device vectors (torch tensors or raw pointer ints; d_x may be d_b).  Returns
+        info (smlu_solve_lowrank_device, ordered after the stream that produced d_b)."""
+        op = _op(trans)
+        steps = _lowrank_steps(steps)
+        self._lowrank_real("solve_lowrank_device")
+        for name, t in (("d_x", d_x), ("d_b", d_b)):
+            _device_f64(name, t, self.n)
+        px = d_x.data_ptr() if hasattr(d_x, "data_ptr") else int(d_x)
+        pb = d_b.data_ptr() if hasattr(d_b, "data_ptr") else int(d_b)
+        ci = C.SmluLowrankInfo()
+        with C.caller_stream(self._h, d_b):
+            rc = _check(C.lib().smlu_solve_lowrank_device(self._h, op, steps, ctypes.c_void_p(pb), ctypes.c_void_p(px),
+                                                          ctypes.byref(ci)), self._h)
+        return _lowrank_info(rc, ci)
 
     def close(self):
         h = getattr(self, "_h", None)
